@@ -12,9 +12,14 @@ when no launcher set WORLD_SIZE); each rank renders its own image's rays, one RC
 of the 3.2 MB flat gradient (with the step's loss terms and PSNR in its tail) per step (DDP
 semantics); weak scaling, value = all ranks' rays / the slowest rank's time.
 
-Prints ONE JSON line (rank 0).  Extra fields: per-kernel live timings (HIP events on the
-launch stream), the roofline record of the dominant kernel, the CPU-oracle baseline and
-the PSNR agreement GPU vs CPU oracle on the same rays.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times ``--steps`` steps and
+prints the line (``ms_per_step``: milliseconds per timed step).  ``--full`` adds, after the
+timed steps: per-kernel live timings (HIP events on the launch stream), the roofline record of
+the dominant kernel, the CPU-oracle baseline and the PSNR agreement GPU vs CPU oracle on the
+same rays.  ``--dump-outputs DIR`` writes what the last timed step returned to its caller
+(dump_outputs) as DIR/<name>.npy; the inputs are seeded and the gradient sums run in fixed
+order (``--reductions ordered``, the default), so a run repeats bit for bit and two builds can
+be compared array for array.
 """
 import argparse
 import json
@@ -132,6 +137,37 @@ def kernel_table(prof, n_units, R, N, fine, stage="b", per_launch=False):
     return ktab, roof
 
 
+DUMP_MAX_ELEMS = 1 << 21   # per array; a larger one is written as a fixed seeded sample
+DUMP_MAX_BYTES = 64 << 20  # all arrays of one dump
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write ``arrays`` (name -> tensor / number; None entries are left out) as
+    dirname/<name>.npy, float32 (float64 stays float64), DUMP_MAX_BYTES in all.  An array of more
+    than DUMP_MAX_ELEMS elements (fewer where the dump would not fit otherwise) is sampled at
+    indices drawn from a generator seeded by its size alone, so two runs -- or two builds --
+    write the same elements."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: torch.as_tensor(v).detach() for k, v in arrays.items() if v is not None}
+    cap = DUMP_MAX_ELEMS   # halved until the whole dump fits
+    while sum(min(t.numel(), cap) * (8 if t.dtype == torch.float64 else 4) for t in arrays.values()) > DUMP_MAX_BYTES:
+        cap //= 2
+    total = 0
+    for name, t in sorted(arrays.items()):
+        t = t.cpu()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(t.numel())
+            idx = torch.randint(t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx]
+        a = t.contiguous().numpy()
+        total += a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    assert total <= DUMP_MAX_BYTES, total
+    progress("outputs written: %d arrays, %.1f MB, %s" % (len(os.listdir(dirname)), total / 2 ** 20, dirname))
+
+
 def run_infer(args, world, rank, dev):
     """configs[4]: syn_hotdog_b video_train inference, size x size frames rendered in
     `chunk`-ray chunks, tile-sharded over the ranks with one all_gather per frame
@@ -172,6 +208,8 @@ def run_infer(args, world, rank, dev):
     barrier()
     PLATFORM.sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # the last timed frame, as Model.inference returned it
+        dump_outputs(args.dump_outputs, {k: v for k, v in out.items() if torch.is_tensor(v)})
     # per-kernel HIP events over one more (untimed) frame rendered with the chunk pipeline off:
     # with two chunks in flight an event pair would also time the other stream's kernels
     n_prof = 0 if args.no_kernel_timing else 1
@@ -500,8 +538,7 @@ def launch_workers(n, argv, script=None, poll_s=0.2):
     return rc or next((p.returncode for p in procs if p.returncode), 0)
 
 
-def main(argv=None):
-    argv = sys.argv[1:] if argv is None else list(argv)
+def parse_args(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
                     help="GPUs of this node; without a launcher's WORLD_SIZE, one process per GPU is spawned")
@@ -541,6 +578,11 @@ def main(argv=None):
                     help="stage-b output-layer dW: on = per-tile partials formed in the heads forward "
                          "(mli_rgb_fwd PQ mode + mli_dw4; X3 never written), off = X3 through HBM and the "
                          "THIN split-K class")
+    ap.add_argument("--reductions", choices=("ordered", "atomic"), default="ordered",
+                    help="train: the backward's split-K dW (and, stage a, hash-grid) sums in fixed order "
+                         "(cfg.trainer.deterministic: a run repeats bit for bit, so --dump-outputs of two runs "
+                         "or two builds can be compared) or with fp32 atomics, whose order varies from run to "
+                         "run and, through AdamW, moves the parameters by 4e-2 within 1000 steps")
     ap.add_argument("--mode", choices=("train", "infer"), default="train",
                     help="train: BASELINE configs[1] step; infer: configs[4] full-frame render")
     ap.add_argument("--frames", type=int, default=4, help="infer: frames timed (after --warmup frames)")
@@ -550,7 +592,21 @@ def main(argv=None):
     ap.add_argument("--iteration", type=int, default=100000,
                     help="stage a (--config syn_hotdog_a): training iteration (sets the coarse-to-fine "
                          "levels, tap epsilon and curvature weight; >= 80000: all 16 levels active)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the "
+                         "per-kernel table and roofline record (extra steps), the CPU-oracle baseline and the "
+                         "PSNR / rgb agreement with it (--no-cpu / --no-kernel-timing leave one of them out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (rank 0)")
     args = ap.parse_args(argv)
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu = args.no_kernel_timing = True
+    return args
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         n_dev = count_gpus()  # sysfs: HIP stays uninitialised in this process
         if n_dev < args.gpus:
@@ -566,6 +622,7 @@ def main(argv=None):
     if rehearse:
         local = 0
     dev = PLATFORM.device(local)
+    torch.manual_seed(1234 + rank)   # the stratified uniforms drawn on the device: the same from run to run
     if world > 1:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -583,6 +640,7 @@ def main(argv=None):
         return run_infer(args, world, rank, dev)
 
     cfg = preset(args.config, rays=args.rays, n_fine=args.fine)
+    cfg.trainer["deterministic"] = args.reductions == "ordered"
     model = Model(cfg.model, cfg.data)
     stage_a = model.stage == "a"
     model.load_state_dict(synthetic.make_state_dict(log2T=22, seed=0, heads="rgb" if stage_a else "rgb_r_s"))
@@ -685,6 +743,17 @@ def main(argv=None):
         elapsed = t.item()
     psnr = trainer.metrics["psnr"].item()
     loss = trainer.losses["total"].item()
+    if args.dump_outputs and rank == 0:
+        # what train_step leaves its caller after the last timed step: the loss terms and PSNR, the
+        # render outputs of its batch, the flat gradient and the updated parameters
+        arrays = {"loss_" + k: v for k, v in trainer.losses.items()}
+        arrays["psnr"] = trainer.metrics["psnr"]
+        arrays.update({"out_" + k: v for k, v in model.outputs(model._last_state).items()})
+        arrays["grad"] = model.flat.grad
+        arrays["params"] = model.flat
+        if stage_a:
+            arrays["params_table"] = model.neural_sdf.tcnn_encoding.params
+        dump_outputs(args.dump_outputs, arrays)
     k_steps = args.steps
     if pipe and not args.no_kernel_timing:
         # with the prefetch on, an event pair on one stream also times the other stream's
@@ -715,8 +784,9 @@ def main(argv=None):
                    "samples_per_ray": N, "global_rays": R * world, "image": [Hh, W], "parallelism": "dp%d" % world,
                    "pipeline": ("geometry prefetch on a side stream, gate %s, %d batch(es) ahead" % (args.pipeline, depth)) if pipe else "off",
                    "output_layer_dw": "forward partials (pq)" if args.pq == "on" else "THIN split-K",
-                   "tail": args.tail},
-        "kernel_timing": ("HIP events on the launch stream over %d extra steps with the prefetch off" % k_steps)
+                   "tail": args.tail, "reductions": args.reductions},
+        "kernel_timing": "off (--full measures the per-kernel table)" if args.no_kernel_timing else
+        ("HIP events on the launch stream over %d extra steps with the prefetch off" % k_steps)
         if pipe else "HIP events on the launch stream over the timed steps",
         "psnr": round(psnr, 4), "loss": round(loss, 6),
         "roofline": roof, "kernels": ktab,

@@ -106,6 +106,38 @@ def test_launcher_refuses_while_holding_a_gpu_file(monkeypatch):
         bench.launch_workers(2, ["--steps", "1"], script=os.path.join(ROOT, "bench.py"))
 
 
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: every array as float32 (float64 kept), None left out, a large array as the
+    same seeded sample on every call."""
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=torch.float32)
+    arrays = {"rgb": torch.rand(1, 5, 3), "mask": torch.tensor([True, False]), "d": torch.ones(2, dtype=torch.float64),
+              "loss": torch.tensor(0.5), "none": None, "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("rgb", "mask", "d", "loss", "big")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "d.npy", "loss.npy", "mask.npy", "rgb.npy"]
+    assert got["rgb"].dtype == np.float32 and np.array_equal(got["rgb"], arrays["rgb"].numpy())
+    assert got["mask"].dtype == np.float32 and got["mask"].tolist() == [1.0, 0.0]
+    assert got["d"].dtype == np.float64 and got["loss"].shape == ()
+    assert got["big"].shape == (bench.DUMP_MAX_ELEMS,)
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert np.array_equal(got["big"], big.numpy()[got["big"].astype(np.int64)])   # elements of the array itself
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    """Without --full the run asks for neither the per-kernel table nor the CPU baseline."""
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert plain.no_cpu and plain.no_kernel_timing and plain.steps == 3 and plain.dump_outputs is None
+    assert plain.reductions == "ordered"   # a run repeats bit for bit (tests/test_gpu_determinism.py)
+    full = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert not full.no_cpu and not full.no_kernel_timing and full.dump_outputs == "d"
+    assert bench.parse_args(["--full", "--no-cpu"]).no_cpu
+
+
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("mode", ["train", "infer"])
 def test_bench_main_gpus2_end_to_end(mode, tmp_path, capfd, monkeypatch):

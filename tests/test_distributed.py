@@ -437,7 +437,7 @@ def test_bench_launcher_world2(tmp_path, capfd):
     assert bench.launch_workers(WORLD, ["--fail"], script=str(w)) == 3
 
 
-def _zero_guard_worker(rank, world, port, results):
+def _zero_guard_worker(rank, world, port, results, logdir):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -458,7 +458,7 @@ def _zero_guard_worker(rank, world, port, results):
         tr.train_step(synthetic.make_batch(32, frame=rank + 10))
         tr.train_step(synthetic.make_batch(32, frame=rank + 20))   # two steps without a sync
         for what, fn in (("optim_state_dict", tr.optim_state_dict),
-                         ("save_checkpoint", lambda: tr.save_checkpoint("/nonexistent-not-written")),
+                         ("save_checkpoint", lambda: tr.save_checkpoint(os.path.join(logdir, "not-written-%d" % rank))),
                          ("prepare", lambda: (setattr(m, "engine", None), setattr(m, "_sdf_version", None),
                                               m.prepare()))):
             try:
@@ -477,7 +477,7 @@ def _zero_guard_worker(rank, world, port, results):
 
 
 @pytest.mark.timeout(300)
-def test_zero_table_stale_state_guards():
+def test_zero_table_stale_state_guards(tmp_path):
     """with the table ZeRO-sharded, the fp32 master outside this rank's shard and the
     gathered moments are only valid right after sync_table().  Two steps without a sync must make
     optim_state_dict, save_checkpoint and an engine rebuild (Model.prepare re-casting the fp16
@@ -486,10 +486,11 @@ def test_zero_table_stale_state_guards():
     port = _free_port()
     ctx = mp.get_context("spawn")
     results = ctx.Manager().dict()
-    mp.start_processes(_zero_guard_worker, args=(2, port, results), nprocs=2, join=True, start_method="spawn")
+    mp.start_processes(_zero_guard_worker, args=(2, port, results, str(tmp_path)), nprocs=2, join=True, start_method="spawn")
     for r in range(2):
         assert results[r] == {"optim_state_dict": True, "save_checkpoint": True, "prepare": True,
                               "after_sync": True}, results[r]
+    assert not list(tmp_path.glob("*/*.pt"))   # the refused save wrote no checkpoint
 
 
 def _overlap_worker(rank, port, results):

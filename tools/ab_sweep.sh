@@ -7,9 +7,9 @@ MODE=$2
 shift 2
 mkdir -p "$OUT"
 case $MODE in
-  train) ARGS="--no-cpu --steps 300" ;;
-  infer) ARGS="--no-cpu --mode infer --frames 2 --warmup 1" ;;
-  a) ARGS="--no-cpu --config syn_hotdog_a --steps 100" ;;
+  train) ARGS="--full --no-cpu --steps 300" ;;
+  infer) ARGS="--full --no-cpu --mode infer --frames 2 --warmup 1" ;;
+  a) ARGS="--full --no-cpu --config syn_hotdog_a --reductions atomic --steps 100" ;;
 esac
 i=0
 for lib in "$@"; do
