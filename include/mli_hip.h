@@ -52,7 +52,7 @@ extern "C" {
 
 typedef struct ihipStream_t* mli_stream_t; /* == hipStream_t */
 
-#define MLI_ABI_VERSION 17
+#define MLI_ABI_VERSION 18
 #define MLI_HIDDEN 256
 #define MLI_LEVELS 16
 #define MLI_LEVEL_FEAT 8
@@ -255,6 +255,9 @@ typedef struct {
                              (scaled)                                                        */
   uint16_t* dz4T;         /* [3 heads] x [S/32][1][64][8] frag images of dZ4 (rows 0..2, scaled),
                              or NULL (PQ mode: the output-layer dW comes from mli_dw4)         */
+  int skip_dz3;           /* ABI 18: 1 = the dZ3 images (layer 3 of every head) are not stored and
+                             their part of dzT is left untouched: mli_wgrad rebuilds them
+                             (mli_wgrad_job.rb_*)                                              */
 } mli_rgb_bwd_args;
 int mli_rgb_bwd(const mli_rgb_bwd_args* a, mli_stream_t s);
 /* bytes[0..1]: dzT, dz4T. */
@@ -288,6 +291,15 @@ typedef struct {
                               frag image (b2_kst k-steps per tile, B's order and tile count) -- the
                               SDF layer-0 input [enc 128 | p 3] of mli_sdf_bwd (ABI 16)            */
   int b2_q, b2_kst;
+  /* ABI 18, optional (rb_dz4 NULL: A is read from a_rows): A is dZ3 of a colour head, rebuilt in
+   * the kernel as mask3 . (W4^T dz4) by the instruction sequence of mli_rgb_bwd, bit-identical to
+   * the image mli_rgb_bwd stores (which it then need not store: mli_rgb_bwd_args.skip_dz3).
+   * A BIG job of fragment images with M == 256; a_rows is not read. */
+  const float* rb_dz4;    /* [N][R][8] as mli_rgb_bwd_args.dz4 (slot = k * R + r)             */
+  const uint32_t* rb_mask; /* the head's layer-3 mask image [S/32][64][4] (inside masks)       */
+  const void* rb_w4;      /* the head's eight W4^T chunks inside wbwd (chunks 32 head + 0..7)  */
+  int rb_col, rb_cnt;     /* the head's dz4 columns: first and count (0/3, 3/3, 6/1)           */
+  int rb_R, rb_N;         /* rb_R * rb_N == S                                                  */
 } mli_wgrad_job;
 #define MLI_WGRAD_LAYOUT_ROWS 0
 #define MLI_WGRAD_LAYOUT_TILED 1

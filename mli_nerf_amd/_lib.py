@@ -69,13 +69,14 @@ class CompositeBwdArgs(C.Structure):
 
 class RgbBwdArgs(C.Structure):
     _fields_ = [("R", I32), ("N", I32), ("dz4", P), ("wbwd", P), ("masks", P), ("dzT", P),
-                ("dz4T", P)]
+                ("dz4T", P), ("skip_dz3", I32)]
 
 
 class WgradJob(C.Structure):
     _fields_ = [("a_rows", P), ("b_rows", P), ("M", I32), ("K", I32), ("dw", P), ("db", P), ("ldw", I32),
                 ("a_tiled", I32), ("b_tiled", I32), ("a_kst", I32), ("b_kst", I32), ("b2_rows", P),
-                ("b2_q", I32), ("b2_kst", I32)]
+                ("b2_q", I32), ("b2_kst", I32), ("rb_dz4", P), ("rb_mask", P), ("rb_w4", P), ("rb_col", I32),
+                ("rb_cnt", I32), ("rb_R", I32), ("rb_N", I32)]
 
 
 # mli_wgrad_job operand layouts (MLI_WGRAD_LAYOUT_*)
@@ -201,7 +202,7 @@ class FragRowsArgs(C.Structure):
                 ("ld", I64), ("col0", I64), ("row0", I32)]
 
 
-ABI_VERSION = 17  # include/mli_hip.h MLI_ABI_VERSION
+ABI_VERSION = 18  # include/mli_hip.h MLI_ABI_VERSION
 
 ENTRY_POINTS = {
     "mli_rays": RaysArgs, "mli_hashgrid_fwd": HashgridArgs, "mli_sdf": SdfArgs,

@@ -46,6 +46,12 @@ MLI_FI half4 ds_tr16_at(uint32_t addr) {
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "i"(OFF));
   return r;
 }
+// A plain 4 B LDS read as inline asm, for the same reason (wait with lgkm_wait(), then tie()).
+MLI_FI uint32_t ds_read_u32(uint32_t addr) {
+  uint32_t r;
+  asm volatile("ds_read_b32 %0, %1" : "=v"(r) : "v"(addr));
+  return r;
+}
 // A 16 B global load as inline asm.  Loads, stores and LDS-DMAs of a wave retire in issue order
 // (MI355X_MICROARCH.md, vmcnt), but the compiler treats a counter with loads AND stores pending
 // as out of order and waits vmcnt(0) for any load result -- draining the weight DMAs and the
@@ -140,6 +146,13 @@ MLI_FI half8 acc_to_frag(const f32x16& v, int s) {
     w[p] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, half2));
   }
   return __builtin_bit_cast(half8, w);
+}
+
+// acc where bit `bit` of `bits` is set, else +0 (the ReLU derivative from the forward's mask
+// bits): a signed one-bit field extract (0 / -1) and an and, two VALU per element (the compiler's
+// form -- and, compare, select -- took three).
+MLI_FI float mask_bit(float x, uint32_t bits, int bit) {
+  return __builtin_bit_cast(float, __builtin_bit_cast(int, x) & __builtin_amdgcn_sbfe((int)bits, bit, 1));
 }
 
 // torch.nn.functional.softplus(x, beta=100, threshold=20) as max(x, 0) + log(1 + e^{-|t|}) / 100,

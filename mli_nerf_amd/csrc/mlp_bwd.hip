@@ -3,10 +3,11 @@
 
 namespace {
 
+template <bool NODZ3>
 __global__ __launch_bounds__(GBwd::THREADS) void rgb_bwd_kernel(mli_rgb_bwd_args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= GBwd::NW / 2) rgb_bwd_body<GBwd, STORE>(a, lds);
-  else rgb_bwd_body<GBwd, DMA>(a, lds);
+  if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= GBwd::NW / 2) rgb_bwd_body<GBwd, STORE, NODZ3>(a, lds);
+  else rgb_bwd_body<GBwd, DMA, NODZ3>(a, lds);
 }
 
 
@@ -15,8 +16,12 @@ __global__ __launch_bounds__(GBwd::THREADS) void rgb_bwd_kernel(mli_rgb_bwd_args
 extern "C" int mli_rgb_bwd(const mli_rgb_bwd_args* a, mli_stream_t s) {
   const int S = a->R * a->N;
   if (S % 256 != 0) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(rgb_bwd_kernel, dim3(S / GBwd::SAMPLES), dim3(GBwd::THREADS), GBwd::LDS_BWD, (hipStream_t)s,
-                     *a);
+  if (a->skip_dz3)
+    hipLaunchKernelGGL(rgb_bwd_kernel<true>, dim3(S / GBwd::SAMPLES), dim3(GBwd::THREADS), GBwd::LDS_BWD,
+                       (hipStream_t)s, *a);
+  else
+    hipLaunchKernelGGL(rgb_bwd_kernel<false>, dim3(S / GBwd::SAMPLES), dim3(GBwd::THREADS), GBwd::LDS_BWD,
+                       (hipStream_t)s, *a);
   MLI_LAUNCH_CHECK();
 }
 

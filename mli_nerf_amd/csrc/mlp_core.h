@@ -191,12 +191,7 @@ MLI_FI uint32_t relu_bits16(const f32x16& r) {
     asm("v_cmp_lt_i32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(b) : "v"(f32_bits(r[i])) : "vcc");
   return b;
 }
-// acc where bit `bit0 + i` of `bits` is set, else +0 (the backward's ReLU derivative): a signed
-// one-bit field extract (0 / -1) and an and, two VALU per element (the compiler's form -- and,
-// compare, select -- took three).
-MLI_FI float mask_bit(float x, uint32_t bits, int bit) {
-  return __builtin_bit_cast(float, __builtin_bit_cast(int, x) & __builtin_amdgcn_sbfe((int)bits, bit, 1));
-}
+// (the backward's ReLU derivative from these bits: mask_bit, common.h)
 // acc = W_chunk (32 x 16*KS) * X (16*KS x 32) + bias.  PF = 0: the compiler's schedule (it reads
 // two weight fragments ahead and waits lgkmcnt(0) before every MFMA pair, so each pair pays the
 // LDS latency); PF > 0: the fragments are read PF ahead, one read issued after each MFMA (the
@@ -742,7 +737,9 @@ __global__ __launch_bounds__(GFwd::THREADS) void rgb_fwd_kernel(mli_rgb_fwd_args
 MLI_FI int bwd_bytes(int c) { return (c % 32) < 8 ? CH(1) : CH(16); }
 constexpr int BWD_CHUNKS = 3 * 32;
 
-template <class G, int ROLE>
+// NODZ3 (mli_rgb_bwd_args.skip_dz3): the layer-3 epilogue still forms the dZ3 fragments for the
+// chain but does not store them (mli_wgrad rebuilds them from dz4, the mask and W4^T).
+template <class G, int ROLE, bool NODZ3 = false>
 MLI_FI void rgb_bwd_body(const mli_rgb_bwd_args& a, uint8_t* lds) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
@@ -820,8 +817,8 @@ MLI_FI void rgb_bwd_body(const mli_rgb_bwd_args& a, uint8_t* lds) {
       }
     };
     auto pre = [&](int li) MLI_LAMBDA_FI { return MaskPre{mask_dma, hd * 4 + li + 1}; };
-    auto mask_epi = [&](half8* out, int layer /* dZ index */, int li) MLI_LAMBDA_FI {
-      return [&, out, layer, li](int t, const f32x16& acc) MLI_LAMBDA_FI {
+    auto mask_epi = [&](half8* out, int layer /* dZ index */, int li, auto stc /* stored? */) MLI_LAMBDA_FI {
+      return [&, out, layer, li, stc](int t, const f32x16& acc) MLI_LAMBDA_FI {
         const u32x4 mv =
             *reinterpret_cast<const u32x4*>(lds + G::MASK_OFF + (li & 1) * G::MASKB + wave * 1024 + lane * 16);
         const int wi = t >> 1;
@@ -831,14 +828,16 @@ MLI_FI void rgb_bwd_body(const mli_rgb_bwd_args& a, uint8_t* lds) {
         for (int i = 0; i < 16; ++i) v[i] = mask_bit(acc[i], word, (t & 1) * 16 + i);
         out[2 * t] = acc_to_frag(v, 0);
         out[2 * t + 1] = acc_to_frag(v, 1);
-        frag_store2(a.dzT + ((size_t)(hd * 4 + layer) * (S / 32) + tile) * FRAG_TILE, t, out[2 * t], out[2 * t + 1],
-                    lane);
+        if (decltype(stc)::value)
+          frag_store2(a.dzT + ((size_t)(hd * 4 + layer) * (S / 32) + tile) * FRAG_TILE, t, out[2 * t],
+                      out[2 * t + 1], lane);
       };
     };
-    auto e3 = mask_epi(A, 3, 0);
-    auto e2 = mask_epi(B, 2, 1);
-    auto e1 = mask_epi(A, 1, 2);
-    auto e0 = mask_epi(B, 0, 3);
+    const std::true_type store{};
+    auto e3 = mask_epi(A, 3, 0, std::integral_constant<bool, !NODZ3>{});
+    auto e2 = mask_epi(B, 2, 1, store);
+    auto e1 = mask_epi(A, 1, 2, store);
+    auto e0 = mask_epi(B, 0, 3, store);
     auto none = [](f32x16&) MLI_LAMBDA_FI {};
     auto fin = [&](auto& e) MLI_LAMBDA_FI {
       return [&](f32x16& p) MLI_LAMBDA_FI {
@@ -847,10 +846,10 @@ MLI_FI void rgb_bwd_body(const mli_rgb_bwd_args& a, uint8_t* lds) {
     };
     f32x16 pacc;
     // static store counts: 2 dZ fragments per epilogue (EPI, PREVN and the previous layer's last
-    // phase, LASTN)
-    constexpr int X = 2, LN = X;
-    heads_layer<G, ROLE, 1, 8, X, 0, 0, HEADS_DEFER, 0, 2>(rg, lds, &z4, lane, bytes, pre(0), none, e3, pacc);
-    heads_layer<G, ROLE, 16, 8, X, 0, X, HEADS_DEFER, LN, 2>(rg, lds, A, lane, bytes, pre(1), fin(e3), e2, pacc);
+    // phase, LASTN); X3: those of the dZ3 epilogues
+    constexpr int X = 2, LN = X, X3 = NODZ3 ? 0 : X;
+    heads_layer<G, ROLE, 1, 8, X3, 0, 0, HEADS_DEFER, 0, 2>(rg, lds, &z4, lane, bytes, pre(0), none, e3, pacc);
+    heads_layer<G, ROLE, 16, 8, X, 0, X3, HEADS_DEFER, X3, 2>(rg, lds, A, lane, bytes, pre(1), fin(e3), e2, pacc);
     heads_layer<G, ROLE, 16, 8, X, 0, X, HEADS_DEFER, LN, 2>(rg, lds, B, lane, bytes, pre(2), fin(e2), e1, pacc);
     heads_layer<G, ROLE, 16, 8, X, 0, X, HEADS_DEFER, LN, 2>(rg, lds, A, lane, bytes, pre(3), fin(e1), e0, pacc);
     if (HEADS_DEFER) e0(7, pacc);  // the head's last tile (its mask slot is not refilled before the

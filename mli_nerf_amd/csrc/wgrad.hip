@@ -30,6 +30,9 @@ struct Job {
   int a_kst, b_kst;      // frag images: k-steps per 32-sample tile
   const uint16_t* b2;    // frag images: B's k-steps b2_q .. from this image (b2_kst per tile), or NULL
   int b2_q, b2_kst;
+  // A rebuilt in the kernel (mli_wgrad_job rb_*; rb_dz4 NULL: A is read from its image)
+  const float* rb_dz4; const uint8_t* rb_mask; const uint8_t* rb_w4;
+  int rb_col, rb_cnt, rb_R, rb_N;
 };
 
 // Address of (row, sample k .. k + 63) of an operand with n_rows rows: feature-major rows or the
@@ -368,6 +371,12 @@ MLI_FI int frag_read_off(int lane, int half, int r, bool nat) {
   return (g & 1) * 1024 + frag_chunk(c, hh, g & 1) * 16 + b8;
 }
 
+// the instantiations that take rebuild jobs (see the kernel), the LDS bytes of one stage's
+// rebuild inputs (dz4 rows, mask tile) and of a W4^T chunk (one k-step + 32 fp32 biases: CH(1)
+// of mlp_core.h)
+constexpr bool rebuild_ok(int BM, int BN, bool SHARE_B, int TPS) { return BM == 256 && BN == 256 && !SHARE_B && TPS == 1; }
+constexpr int E_SLOT = 2048, W4_CHUNK = 1024 + 128;
+
 template <int BM, int BN, int WM, int WN, int NBUF, bool SHARE_B, int TPS>
 __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
@@ -377,6 +386,14 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
   constexpr int STAGE = PIECES * 1024, B_OFF = TPS * KA * 1024, STG = 32 * TPS;
   static_assert(64 % STG == 0, "the k-slices are whole stages");
   static_assert(KA % 2 == 0 && KB % 2 == 0, "operand blocks of whole 32-feature tiles");
+  // Rebuild jobs (rb_dz4 set): the A operand is dZ3 = mask3 . (W4^T dz4) of a colour head, and
+  // the eight waves write the A block of a stage into LDS themselves -- wave w the 32-feature
+  // tile w (k-steps 2 w, 2 w + 1) by the instruction sequence of rgb_bwd_body's layer-3 phase --
+  // instead of the image going through HBM.  Only where the eight waves' tiles are the whole A
+  // block (BIG); A_PPW: the A pieces are the first A_PPW of a wave's PPW.  Waves 0 / 1 DMA the
+  // stage's dz4 rows / mask tile (1 KiB each) into one of NBUF extra slots behind the ring.
+  constexpr bool CAN_RB = rebuild_ok(BM, BN, SHARE_B, TPS);
+  constexpr int A_PPW = TPS * KA / 8, E_OFF = NBUF * STAGE;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   int bid = blockIdx.x;
   if (SHARE_B) {  // as wgrad_kernel
@@ -430,10 +447,12 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
   }
   // lane (c, hh) of an even k-step's piece: 16 B at (32 hh + (c ^ 4 hh)) * 16; odd: c ^ 8 as well
   const uint32_t voff = (32 * (lane >> 5) + ((lane & 31) ^ ((lane >> 5) << 2))) * 16;
-  auto issue = [&](int s, int buf) MLI_LAMBDA_FI {
+  // RB (a rebuild job, below): only the B pieces; the A block is written by the waves
+  auto issue = [&](auto RBc, int s, int buf) MLI_LAMBDA_FI {
+    constexpr int U0 = decltype(RBc)::value ? A_PPW : 0;
     const int kk = min(k0 + s * STG, k1 - STG);  // past the end: a dummy refetch, never consumed
 #pragma unroll
-    for (int u = 0; u < PPW; ++u) {
+    for (int u = U0; u < PPW; ++u) {
       const uint8_t* sp = sbase[u] + (size_t)(kk >> 5) * tstride[u];
       glds16(sp + (voff ^ (uint32_t)odd[u]), lds + buf * STAGE + piece_of(u) * 1024);
     }
@@ -470,12 +489,8 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
   const half2 ones = {(f16)1.f, (f16)1.f};
 
   const int n_st = (k1 - k0) / STG;
-#pragma unroll
-  for (int d = 0; d < NBUF - 1; ++d) issue(d, d);
-  for (int st = 0; st < n_st; ++st) {
-    vm_wait((NBUF - 2) * PPW);  // this wave's DMAs of stage st have landed
-    block_sync();               // ... every wave's; and everyone is done with stage st - 1
-    issue(st + NBUF - 1, (st + NBUF - 1) % NBUF);
+  // the MFMAs of stage st (its operand blocks are in LDS buffer st % NBUF)
+  auto consume = [&](int st) MLI_LAMBDA_FI {
     const uint32_t so = (st % NBUF) * STAGE;
     // The 2 TPS MFMA k-steps of the stage.  A fragments double-buffered: k-step ks + 1's go out
     // at the start of k-step ks.  B fragments single-buffered, refilled progressively: the MFMAs
@@ -525,6 +540,114 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
             bsum[i] = __builtin_amdgcn_fdot2(half2{fa[cb][i][e], fa[cb][i][e + 1]}, ones, bsum[i], false);
       }
     });
+  };
+  // the ring over both operands' images
+  auto stream = [&]() MLI_LAMBDA_FI {
+    const std::false_type img{};
+#pragma unroll
+    for (int d = 0; d < NBUF - 1; ++d) issue(img, d, d);
+    for (int st = 0; st < n_st; ++st) {
+      vm_wait((NBUF - 2) * PPW);  // this wave's DMAs of stage st have landed
+      block_sync();               // ... every wave's; and everyone is done with stage st - 1
+      issue(img, st + NBUF - 1, (st + NBUF - 1) % NBUF);
+      consume(st);
+    }
+  };
+  if constexpr (CAN_RB) {
+    if (J.rb_dz4 != nullptr) {
+      // The same ring for B alone.  Iteration st also issues the rebuild inputs E of stage
+      // st + NBUF (before its B DMAs, so that B(st) landed implies E(st + 1) landed: no wait of
+      // its own) and, after its MFMAs, writes the A block of stage st + 1 -- into a buffer whose A
+      // region no DMA touches and whose last readers passed the barrier of iteration st - 2; the
+      // barrier of iteration st + 1 publishes it.  The LDS operations of the rebuild all come
+      // after the stage's counted lgkmcnt waits, and the vmcnt counts are per wave role: waves
+      // 0 / 1 issue one more DMA per stage than the others.
+      const std::true_type rb{};
+      constexpr int B_PPW = PPW - A_PPW;
+      const int c = lane & 31;
+      const uint32_t l0 = lds_addr(lds);
+      // this wave's W4^T fragment and the chunk's biases (the accumulator's initial value, as
+      // chunk_mma<1>): held for the whole slice; loaded before the first DMA goes out
+      const uint8_t* wc = J.rb_w4 + wv * W4_CHUNK;
+      half8 wf = *reinterpret_cast<const half8*>(wc + lane * 16);
+      f32x16 bias;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const f32x4 b = *reinterpret_cast<const f32x4*>(wc + 1024 + h * 64 + u * 16);
+        bias[4 * u] = b[0]; bias[4 * u + 1] = b[1]; bias[4 * u + 2] = b[2]; bias[4 * u + 3] = b[3];
+      }
+      tie(wf);
+      tie(bias);
+      auto issue_e = [&](int s) MLI_LAMBDA_FI {
+        if (wv < 2) {
+          const int kk = min(k0 + s * STG, k1 - STG);
+          const uint8_t* p;
+          if (wv == 0) {  // lane (c, hh): floats 4 hh .. 4 hh + 3 of sample c's dz4 row
+            const int m = kk + c, r = m / J.rb_N, k = m - r * J.rb_N;
+            p = reinterpret_cast<const uint8_t*>(J.rb_dz4) + ((size_t)k * J.rb_R + r) * 32 + h * 16;
+          } else {
+            p = J.rb_mask + (size_t)(kk >> 5) * 1024 + lane * 16;
+          }
+          glds16(p, lds + E_OFF + (s % NBUF) * E_SLOT + wv * 1024);
+        }
+      };
+      auto rebuild = [&](int s) MLI_LAMBDA_FI {
+        const uint32_t e = l0 + E_OFF + (s % NBUF) * E_SLOT;
+        // dz4 columns rb_col .. rb_col + 2 of sample c (clamped to the row; rb_cnt of them used)
+        uint32_t d[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const int f = min(J.rb_col + i, 7);
+          d[i] = ds_read_u32(e + ((f >> 2) * 32 + c) * 16 + (f & 3) * 4);
+        }
+        uint32_t word = ds_read_u32(e + 1024 + lane * 16 + (wv >> 1) * 4);
+        lgkm_wait<0>();
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tie(d[i]);
+        tie(word);
+        // the one-k-step fragment z4, the MFMA, the mask and the conversion as rgb_bwd_body
+        half8 z4;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) z4[j] = (f16)0.f;
+        if (h == 0) {
+          z4[0] = (f16)__builtin_bit_cast(float, d[0]);
+          if (J.rb_cnt > 1) {
+            z4[1] = (f16)__builtin_bit_cast(float, d[1]);
+            z4[2] = (f16)__builtin_bit_cast(float, d[2]);
+          }
+        }
+        const f32x16 a = mfma32(wf, z4, bias);
+        f32x16 v;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = mask_bit(a[i], word, (wv & 1) * 16 + i);
+        const uint32_t dst = l0 + (s % NBUF) * STAGE + 2 * wv * 1024;
+        ds_write_f128(dst + frag_chunk(c, h, 0) * 16, __builtin_bit_cast(f32x4, acc_to_frag(v, 0)));
+        ds_write_f128(dst + 1024 + frag_chunk(c, h, 1) * 16, __builtin_bit_cast(f32x4, acc_to_frag(v, 1)));
+      };
+      // as iterations -(NBUF - 1) .. -1 would have issued
+      issue_e(0);
+#pragma unroll
+      for (int d = 0; d < NBUF - 1; ++d) {
+        issue_e(d + 1);
+        issue(rb, d, d);
+      }
+      if (wv < 2) vm_wait((NBUF - 1) * (B_PPW + 1));  // E(0) has landed
+      block_sync();
+      rebuild(0);
+      for (int st = 0; st < n_st; ++st) {
+        if (wv < 2) vm_wait((NBUF - 2) * (B_PPW + 1));  // B(st) -- and E(st + 1), issued before it
+        else vm_wait((NBUF - 2) * B_PPW);
+        block_sync();
+        issue_e(st + NBUF);
+        issue(rb, st + NBUF - 1, (st + NBUF - 1) % NBUF);
+        consume(st);
+        rebuild(st + 1);  // (past the end: the clamped inputs again, into a buffer nobody reads)
+      }
+    } else {
+      stream();
+    }
+  } else {
+    stream();
   }
   vm_wait(0);  // the dummy refetches land before the workgroup's LDS is released
   float* slab = nullptr;
@@ -734,6 +857,11 @@ inline bool job_valid(const mli_wgrad_job& j, int S) {
     return false;
   if (fa && (j.a_kst < (j.M + 15) / 16 || (!j.b2_rows && j.b_kst < (j.K + 15) / 16))) return false;
   if ((j.a_tiled == MLI_WGRAD_LAYOUT_TILED || j.b_tiled == MLI_WGRAD_LAYOUT_TILED) && S % 256 != 0) return false;
+  // a rebuilt A: a whole 256-row BIG block of a fragment job, dz4 columns inside the row
+  if (j.rb_dz4 && (!fa || j.M != 256 || job_class(j) != CLS_BIG || !j.rb_mask || !j.rb_w4 ||
+                   (j.rb_cnt != 1 && j.rb_cnt != 3) || j.rb_col < 0 || j.rb_col + j.rb_cnt > 8 || j.rb_N <= 0 ||
+                   (int64_t)j.rb_R * j.rb_N != S))
+    return false;
   return true;
 }
 
@@ -756,6 +884,10 @@ int64_t plan(const mli_wgrad_args* a, int cls, bool frag, KArgs& ka) {
     J.a_tiled = j.a_tiled; J.b_tiled = j.b_tiled;
     J.a_kst = j.a_kst; J.b_kst = j.b_kst;
     J.b2 = j.b2_rows; J.b2_q = j.b2_q; J.b2_kst = j.b2_kst;
+    J.rb_dz4 = j.rb_dz4;
+    J.rb_mask = reinterpret_cast<const uint8_t*>(j.rb_mask);
+    J.rb_w4 = reinterpret_cast<const uint8_t*>(j.rb_w4);
+    J.rb_col = j.rb_col; J.rb_cnt = j.rb_cnt; J.rb_R = j.rb_R; J.rb_N = j.rb_N;
     J.tiles_n = (j.K + BN - 1) / BN;
     tiles += ((j.M + BM - 1) / BM) * J.tiles_n;
   }
@@ -801,13 +933,17 @@ int launch(const mli_wgrad_args* a, int cls, bool frag, hipStream_t s) {
   if (frag) {
     // fragment images: the LDS-DMA ring, FRAG_NBUF stages of FRAG_TPS tiles
     constexpr int LDS = FRAG_NBUF * FRAG_TPS * (BM / 16 + BN / 16) * 1024;
-    static_assert(LDS <= 160 * 1024, "LDS");
+    // (a launch with rebuild jobs: their inputs' slots behind the ring)
+    constexpr int LDS_RB = rebuild_ok(BM, BN, false, FRAG_TPS) ? FRAG_NBUF * E_SLOT : 0;
+    static_assert(LDS + LDS_RB <= 160 * 1024, "LDS");
+    bool any_rb = false;
+    for (int i = 0; i < ka.n_jobs; ++i) any_rb = any_rb || ka.jobs[i].rb_dz4 != nullptr;
     if (SHARE_B && ka.share)
       hipLaunchKernelGGL((wgrad_frag_kernel<BM, BN, WM, WN, FRAG_NBUF, SHARE_B, FRAG_TPS>),
                          dim3(8 * ka.n_jobs * ((ka.n_split + 7) / 8)), dim3(512), LDS, s, ka);
     else
-      hipLaunchKernelGGL((wgrad_frag_kernel<BM, BN, WM, WN, FRAG_NBUF, false, FRAG_TPS>), dim3(grid), dim3(512), LDS,
-                         s, ka);
+      hipLaunchKernelGGL((wgrad_frag_kernel<BM, BN, WM, WN, FRAG_NBUF, false, FRAG_TPS>), dim3(grid), dim3(512),
+                         LDS + (any_rb ? LDS_RB : 0), s, ka);
   } else if (SHARE_B && ka.share) {
     grid = 8 * ka.n_jobs * ((ka.n_split + 7) / 8);
     if constexpr (SHARE_B && DMA_NBUF > 0)

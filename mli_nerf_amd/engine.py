@@ -158,6 +158,10 @@ class RenderEngine:
         # Measured (profiles/r5/slabs, same box): WIDE 0.299 -> 0.265 ms; BIG 0.831 -> 0.840 and
         # THIN 0.143 -> 0.204 ms the other way, stage a slower with its 5S job on slabs.
         self.wgrad_slab_classes = int(os.environ.get("MLI_WGRAD_SLABS", "2"))
+        # backward() given dz4 (the fused train step): mli_rgb_bwd does not store dZ3 and the
+        # layer-3 dW jobs rebuild it from dz4, the ReLU mask and W4^T (mli_wgrad_job.rb_*),
+        # bit-identical; MLI_DZ3_REBUILD=0: the stored image (A/B runs)
+        self.dz3_rebuild = os.environ.get("MLI_DZ3_REBUILD", "1") != "0"
         # stage-b training: the output layers' dW from per-tile partials the heads forward forms
         # while X3 is in registers (mli_rgb_fwd PQ mode + mli_dw4) instead of X3 through HBM and
         # the THIN split-K GEMM; needs N % 32 == 0 (a 32-sample tile within one ray)
@@ -527,13 +531,15 @@ class RenderEngine:
     def _dw_total(self):
         return sum(m * k + m for m, k in self._dw_sizes())
 
-    def _wgrad_plan(self, dzT, dz4T, hd, dwbuf, flat, grad_out, S):
+    def _wgrad_plan(self, dzT, dz4T, hd, dwbuf, flat, grad_out, S, rebuild=None):
         """Split-K jobs (host array) + device assemble descriptors + (PQ mode) the mli_dw4
         output pointers of the layer-4 dW / db; cached per buffer set (a few: Trainer.prefetch
-        alternates two engine lanes, each with its own buffers)."""
+        alternates two engine lanes, each with its own buffers).  ``rebuild``: (dz4, R, N) when
+        the layer-3 jobs rebuild their dZ3 operand (mli_rgb_bwd skip_dz3), else None."""
         pq = hd.get("q4") is not None
         key = (dzT.data_ptr(), None if dz4T is None else dz4T.data_ptr(), hd["x0T"].data_ptr(),
-               hd["xT"].data_ptr(), dwbuf.data_ptr(), flat.data_ptr(), grad_out.data_ptr(), S, pq)
+               hd["xT"].data_ptr(), dwbuf.data_ptr(), flat.data_ptr(), grad_out.data_ptr(), S, pq,
+               None if rebuild is None else (rebuild[0].data_ptr(), hd["masks"].data_ptr()) + tuple(rebuild[1:]))
         hit = self._wplans.get(key)
         if hit is not None:
             return hit
@@ -556,6 +562,13 @@ class RenderEngine:
                 elif li < 4:
                     jobs.append(L.frag_job(L.ptr(dzT[hdx, li]), L.ptr(hd["xT"][hdx, li - 1]), m, k, L.ptr(dw),
                                            L.ptr(db), k, 16, 16))
+                    if li == 3 and rebuild is not None:
+                        # the head's eight W4^T chunks lead its four layers of wbwd
+                        # (layout.bwd_plan); its dz4 columns start at 3 * head
+                        j, (dz4, R, N) = jobs[-1], rebuild
+                        j.rb_dz4, j.rb_mask = L.ptr(dz4), L.ptr(hd["masks"][hdx, 3])
+                        j.rb_w4 = L.ptr(self.wbwd) + self.bplan[4 * hdx]["dst_offset"]
+                        j.rb_col, j.rb_cnt, j.rb_R, j.rb_N = 3 * hdx, k_out, R, N
                 elif pq:
                     dw4[hdx], db4[hdx], k4[hdx] = L.ptr(dw), L.ptr(db), m
                 else:
@@ -608,6 +621,8 @@ class RenderEngine:
         S = N * R
         scale = self.grad_scale(R)
         pq = hd.get("q4") is not None
+        # (the autograd wrapper, dz4 None, keeps the stored dZ3: its callers read dzT afterwards)
+        rebuild = self.dz3_rebuild and dz4 is not None
         if dz4 is None:
             dz4 = self._buf("dz4", (N, R, 8))
             c = lambda t: None if t is None else t.contiguous()  # noqa: E731
@@ -624,8 +639,9 @@ class RenderEngine:
             self._dw_zero = None     # (accumulating from here on, until the assemble zeroes it)
         dzT = self._buf("dzT", (3, 4, S * 256), torch.float16)  # ACC frag images
         L.call("mli_rgb_bwd", L.RgbBwdArgs(R, N, L.ptr(dz4), L.ptr(self.wbwd), L.ptr(hd["masks"]), L.ptr(dzT),
-                                           L.ptr(dz4T)))
-        jobs, ad, (dw4, db4, k4) = self._wgrad_plan(dzT, dz4T, hd, dwbuf, flat, grad_out, S)
+                                           L.ptr(dz4T), 1 if rebuild else 0))
+        jobs, ad, (dw4, db4, k4) = self._wgrad_plan(dzT, dz4T, hd, dwbuf, flat, grad_out, S,
+                                                    (dz4, R, N) if rebuild else None)
         if self.gate_wgrad:  # Trainer.prefetch(gate="wgrad"): next geometry may start here
             self.gate_event = torch.cuda.Event()
             self.gate_event.record()

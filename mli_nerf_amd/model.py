@@ -254,6 +254,7 @@ class Model(torch.nn.Module):
         self.image_width = self.image_size_train[1]
         self.deterministic = False  # fixed-order gradient reductions (RenderEngine.deterministic)
         self.pq = True              # stage-b output-layer dW from the forward's partials (RenderEngine.pq)
+        self.dz3_rebuild = None     # True / False: override RenderEngine.dz3_rebuild (None: its default)
 
     # -------------------------------------------------------------- parameter plumbing
     def _view(self, name, flat=None):
@@ -379,6 +380,8 @@ class Model(torch.nn.Module):
         eng = self.engine
         eng.deterministic = self.deterministic
         eng.pq = self.pq
+        if self.dz3_rebuild is not None:
+            eng.dz3_rebuild = self.dz3_rebuild
         eng.set_normal_eps(sdf.normal_eps)
         eng.active_levels = int(sdf.active_levels)
         l0 = sdf.mlp.linears[0]
