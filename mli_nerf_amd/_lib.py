@@ -226,6 +226,23 @@ WORKSPACE = {
     "mli_pack": 1, "mli_dw4": 1, "mli_composite_loss": 2,
 }
 
+
+# ---------------------------------------------------------------- include/mli_mesh.h
+class McArgs(C.Structure):
+    _fields_ = [("sdf", P), ("nx", I32), ("ny", I32), ("nz", I32), ("sx", I64), ("sy", I64), ("sz", I64),
+                ("iso", F32), ("origin", F32 * 3), ("spacing", F32), ("off_x", I32), ("off_y", I32),
+                ("off_z", I32), ("gx", I32), ("gy", I32), ("gz", I32), ("chunk_base", P), ("counts", P),
+                ("edge_slot", P), ("max_vertices", I32), ("max_triangles", I32), ("verts", P),
+                ("vert_keys", P), ("faces", P), ("face_keys", P)]
+
+
+MESH_ABI_VERSION = 1  # include/mli_mesh.h MLI_MESH_ABI_VERSION
+MC_CHUNK = 256        # MLI_MC_CHUNK
+
+# the iso-surface ops, versioned apart from the rendering ABI above (ENTRY_POINTS / WORKSPACE)
+MESH_ENTRY_POINTS = {"mli_mc_count": McArgs, "mli_mc_emit": McArgs}
+MESH_WORKSPACE = {"mli_mc_count": 2, "mli_mc_emit": 1}
+
 _lib = None
 
 
@@ -236,19 +253,21 @@ def lib():
             raise ImportError("libmli_hip.so is not built (%s); run mli_nerf_amd.build.build() -- "
                               "there is no CPU fallback for the hot path" % LIB_PATH)
         _lib = C.CDLL(LIB_PATH)
-        for name, st in ENTRY_POINTS.items():
+        for name, st in list(ENTRY_POINTS.items()) + list(MESH_ENTRY_POINTS.items()):
             fn = getattr(_lib, name)
             fn.argtypes = [C.POINTER(st), P]
             fn.restype = I32
-        for name in WORKSPACE:
-            fn = getattr(_lib, name + "_workspace")
-            fn.argtypes = [C.POINTER(ENTRY_POINTS[name]), C.POINTER(I64)]
-            fn.restype = I32
+        for table, points in ((WORKSPACE, ENTRY_POINTS), (MESH_WORKSPACE, MESH_ENTRY_POINTS)):
+            for name in table:
+                fn = getattr(_lib, name + "_workspace")
+                fn.argtypes = [C.POINTER(points[name]), C.POINTER(I64)]
+                fn.restype = I32
+        _lib.mli_mesh_abi_version.restype = I32
         _lib.mli_abi_version.restype = I32
         _lib.mli_error_string.restype = C.c_char_p
         _lib.mli_error_string.argtypes = [I32]
         _lib.mli_source_hash.restype = C.c_char_p
-        if _lib.mli_abi_version() != ABI_VERSION:
+        if _lib.mli_abi_version() != ABI_VERSION or _lib.mli_mesh_abi_version() != MESH_ABI_VERSION:
             raise ImportError("libmli_hip.so ABI mismatch")
         from . import build as _build
         # in-tree sources: the in-tree library must match them.  Only a library OUTSIDE the in-tree
@@ -281,7 +300,7 @@ def workspace(name, args):
     rc = getattr(lib(), name + "_workspace")(C.byref(args), out)
     if rc != 0:
         raise RuntimeError("%s_workspace failed: %s (%d)" % (name, lib().mli_error_string(rc).decode(), rc))
-    return [int(out[i]) for i in range(WORKSPACE[name])]
+    return [int(out[i]) for i in range((WORKSPACE.get(name) or MESH_WORKSPACE[name]))]
 
 
 def ptr(t):
