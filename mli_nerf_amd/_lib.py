@@ -243,6 +243,42 @@ MC_CHUNK = 256        # MLI_MC_CHUNK
 MESH_ENTRY_POINTS = {"mli_mc_count": McArgs, "mli_mc_emit": McArgs}
 MESH_WORKSPACE = {"mli_mc_count": 2, "mli_mc_emit": 1}
 
+# ---------------------------------------------------------------- include/mli_labels.h
+class LabelMorphArgs(C.Structure):
+    _fields_ = [("B", I32), ("H", I32), ("W", I32), ("erode_radius", I32), ("edge_step", I32),
+                ("visibility", P), ("eroded", P), ("certainty", P), ("tile_max", P), ("normal_x_light", P),
+                ("inter_mask", P), ("inv_gamma", F32), ("shading", P), ("shading_gamma", P)]
+
+
+class LabelKmeansArgs(C.Structure):
+    _fields_ = [("L", I32), ("K", I32), ("n_pixels", I32), ("max_iter", I32), ("image", P), ("labels", P),
+                ("centers", P), ("passes", P)]
+
+
+class LabelBestRefArgs(C.Structure):
+    _fields_ = [("L", I32), ("K", I32), ("n_pixels", I32), ("threshold", F32), ("threshold_wrt_max", F32),
+                ("image", P), ("shading", P), ("shading_gamma", P), ("labels", P), ("average_ref", P),
+                ("keep_count", P), ("any_mask", P)]
+
+
+class LabelFillArgs(C.Structure):
+    _fields_ = [("H", I32), ("W", I32), ("K", I32), ("n_holes", I32), ("n_donors", I32), ("slices", I32),
+                ("normal", P), ("centers", P), ("hole_idx", P), ("donor_idx", P), ("ref", P), ("hole_feat", P),
+                ("donor_feat", P), ("partial", P)]
+
+
+LABELS_ABI_VERSION = 1     # include/mli_labels.h MLI_LABELS_ABI_VERSION
+LABELS_MAX_RADIUS = 15     # MLI_LABELS_MAX_RADIUS
+LABELS_MAX_K = 4           # MLI_LABELS_MAX_K
+LABELS_TILE = (32, 8)      # MLI_LABELS_TILE_X, MLI_LABELS_TILE_Y
+LABELS_DONOR_TILE = 256    # MLI_LABELS_DONOR_TILE
+LABELS_MAX_SLICES = 64     # MLI_LABELS_MAX_SLICES
+
+# the pseudo-label ops, versioned apart from both ABIs above
+LABELS_ENTRY_POINTS = {"mli_label_morph": LabelMorphArgs, "mli_label_kmeans": LabelKmeansArgs,
+                       "mli_label_best_ref": LabelBestRefArgs, "mli_label_fill": LabelFillArgs}
+LABELS_WORKSPACE = {"mli_label_morph": 1, "mli_label_fill": 3}
+
 _lib = None
 
 
@@ -253,21 +289,25 @@ def lib():
             raise ImportError("libmli_hip.so is not built (%s); run mli_nerf_amd.build.build() -- "
                               "there is no CPU fallback for the hot path" % LIB_PATH)
         _lib = C.CDLL(LIB_PATH)
-        for name, st in list(ENTRY_POINTS.items()) + list(MESH_ENTRY_POINTS.items()):
+        for name, st in list(ENTRY_POINTS.items()) + list(MESH_ENTRY_POINTS.items()) + list(
+                LABELS_ENTRY_POINTS.items()):
             fn = getattr(_lib, name)
             fn.argtypes = [C.POINTER(st), P]
             fn.restype = I32
-        for table, points in ((WORKSPACE, ENTRY_POINTS), (MESH_WORKSPACE, MESH_ENTRY_POINTS)):
+        for table, points in ((WORKSPACE, ENTRY_POINTS), (MESH_WORKSPACE, MESH_ENTRY_POINTS),
+                              (LABELS_WORKSPACE, LABELS_ENTRY_POINTS)):
             for name in table:
                 fn = getattr(_lib, name + "_workspace")
                 fn.argtypes = [C.POINTER(points[name]), C.POINTER(I64)]
                 fn.restype = I32
         _lib.mli_mesh_abi_version.restype = I32
+        _lib.mli_labels_abi_version.restype = I32
         _lib.mli_abi_version.restype = I32
         _lib.mli_error_string.restype = C.c_char_p
         _lib.mli_error_string.argtypes = [I32]
         _lib.mli_source_hash.restype = C.c_char_p
-        if _lib.mli_abi_version() != ABI_VERSION or _lib.mli_mesh_abi_version() != MESH_ABI_VERSION:
+        if (_lib.mli_abi_version() != ABI_VERSION or _lib.mli_mesh_abi_version() != MESH_ABI_VERSION
+                or _lib.mli_labels_abi_version() != LABELS_ABI_VERSION):
             raise ImportError("libmli_hip.so ABI mismatch")
         from . import build as _build
         # in-tree sources: the in-tree library must match them.  Only a library OUTSIDE the in-tree
@@ -300,7 +340,7 @@ def workspace(name, args):
     rc = getattr(lib(), name + "_workspace")(C.byref(args), out)
     if rc != 0:
         raise RuntimeError("%s_workspace failed: %s (%d)" % (name, lib().mli_error_string(rc).decode(), rc))
-    return [int(out[i]) for i in range((WORKSPACE.get(name) or MESH_WORKSPACE[name]))]
+    return [int(out[i]) for i in range(WORKSPACE.get(name) or MESH_WORKSPACE.get(name) or LABELS_WORKSPACE[name])]
 
 
 def ptr(t):

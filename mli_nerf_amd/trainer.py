@@ -1200,3 +1200,19 @@ class Trainer:
         PNGs and ``results_all.pt`` for scripts/pseudo_label.py (see mli_nerf_amd.relight)."""
         from . import relight
         return relight.test_all_light(self, data_loader, output_dir, mode, dataset_type, sample_num, seed)
+
+    def make_pseudo_labels(self, data_loader, output_dir, setting="pair", images=True, **test_all_light_kwargs):
+        """From a stage-a model to the stage-b label file in one call: ``test_all_light`` (writes
+        ``output_dir/results_all.pt``) followed by ``pseudo_label.write_pseudo_labels`` (writes
+        ``output_dir + '_pseudo_label'/pseudo_label_all.pt``, the path a stage-b config names in
+        ``data.train.pseudo_label.pt_file``).  ``dataset_type`` defaults to the enumeration that
+        goes with ``setting``.  Returns (label dict, path of the label file)."""
+        from . import pseudo_label
+        if setting not in pseudo_label.SETTINGS:
+            raise ValueError("setting %r: one of %s" % (setting, ", ".join(pseudo_label.SETTINGS)))
+        test_all_light_kwargs.setdefault("dataset_type", "unpair" if setting == "unpair" else "pair")
+        results = self.test_all_light(data_loader, output_dir, **test_all_light_kwargs)
+        out_dir = output_dir.rstrip("/") + "_pseudo_label"
+        labels = pseudo_label.write_pseudo_labels(results, out_dir, setting, device=self.model.flat.device,
+                                                  images=images)
+        return labels, os.path.join(out_dir, "pseudo_label_all.pt")
