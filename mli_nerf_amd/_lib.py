@@ -279,6 +279,20 @@ LABELS_ENTRY_POINTS = {"mli_label_morph": LabelMorphArgs, "mli_label_kmeans": La
                        "mli_label_best_ref": LabelBestRefArgs, "mli_label_fill": LabelFillArgs}
 LABELS_WORKSPACE = {"mli_label_morph": 1, "mli_label_fill": 3}
 
+# ---------------------------------------------------------------- include/mli_mesh_cc.h
+class MeshCcArgs(C.Structure):
+    _fields_ = [("faces", P), ("n_faces", I64), ("verts", P), ("n_verts", C.c_int32), ("label", P), ("changed", P),
+                ("max_rounds", C.c_int32), ("round", C.c_int32), ("comp_faces", P), ("comp_area", P), ("max_q", P),
+                ("inv_unit", F64)]
+
+
+MESH_CC_ABI_VERSION = 1    # include/mli_mesh_cc.h MLI_MESH_CC_ABI_VERSION
+MESH_CC_MAX_ROUNDS = 4096  # MLI_CC_MAX_ROUNDS
+
+# the connected-component ops, versioned apart from the three ABIs above
+MESH_CC_ENTRY_POINTS = {"mli_cc_init": MeshCcArgs, "mli_cc_round": MeshCcArgs, "mli_cc_stats": MeshCcArgs}
+MESH_CC_WORKSPACE = {"mli_cc_init": 4}
+
 _lib = None
 
 
@@ -290,24 +304,26 @@ def lib():
                               "there is no CPU fallback for the hot path" % LIB_PATH)
         _lib = C.CDLL(LIB_PATH)
         for name, st in list(ENTRY_POINTS.items()) + list(MESH_ENTRY_POINTS.items()) + list(
-                LABELS_ENTRY_POINTS.items()):
+                LABELS_ENTRY_POINTS.items()) + list(MESH_CC_ENTRY_POINTS.items()):
             fn = getattr(_lib, name)
             fn.argtypes = [C.POINTER(st), P]
             fn.restype = I32
         for table, points in ((WORKSPACE, ENTRY_POINTS), (MESH_WORKSPACE, MESH_ENTRY_POINTS),
-                              (LABELS_WORKSPACE, LABELS_ENTRY_POINTS)):
+                              (LABELS_WORKSPACE, LABELS_ENTRY_POINTS), (MESH_CC_WORKSPACE, MESH_CC_ENTRY_POINTS)):
             for name in table:
                 fn = getattr(_lib, name + "_workspace")
                 fn.argtypes = [C.POINTER(points[name]), C.POINTER(I64)]
                 fn.restype = I32
         _lib.mli_mesh_abi_version.restype = I32
         _lib.mli_labels_abi_version.restype = I32
+        _lib.mli_mesh_cc_abi_version.restype = I32
         _lib.mli_abi_version.restype = I32
         _lib.mli_error_string.restype = C.c_char_p
         _lib.mli_error_string.argtypes = [I32]
         _lib.mli_source_hash.restype = C.c_char_p
         if (_lib.mli_abi_version() != ABI_VERSION or _lib.mli_mesh_abi_version() != MESH_ABI_VERSION
-                or _lib.mli_labels_abi_version() != LABELS_ABI_VERSION):
+                or _lib.mli_labels_abi_version() != LABELS_ABI_VERSION
+                or _lib.mli_mesh_cc_abi_version() != MESH_CC_ABI_VERSION):
             raise ImportError("libmli_hip.so ABI mismatch")
         from . import build as _build
         # in-tree sources: the in-tree library must match them.  Only a library OUTSIDE the in-tree
@@ -340,7 +356,8 @@ def workspace(name, args):
     rc = getattr(lib(), name + "_workspace")(C.byref(args), out)
     if rc != 0:
         raise RuntimeError("%s_workspace failed: %s (%d)" % (name, lib().mli_error_string(rc).decode(), rc))
-    return [int(out[i]) for i in range(WORKSPACE.get(name) or MESH_WORKSPACE.get(name) or LABELS_WORKSPACE[name])]
+    return [int(out[i]) for i in range(WORKSPACE.get(name) or MESH_WORKSPACE.get(name) or LABELS_WORKSPACE.get(name)
+                                         or MESH_CC_WORKSPACE[name])]
 
 
 def ptr(t):

@@ -7,16 +7,22 @@ Replaces projects/neuralangelo/scripts/extract_mesh.py + projects/neuralangelo/u
 * ``extract_mesh(model, ...)``: the model's SDF on a lattice in blocks (the existing mli_sdf SDF
   mode, a lattice column along z as a pseudo-ray), marching cubes per block, the blocks welded by
   vertex key, optional per-vertex normals (FIELD mode) and colours (the heads, under a stated light);
+* ``connected_components(faces, n_verts, verts)`` / ``filter_components(mesh, ...)``: the mesh's
+  components, their face counts and areas (include/mli_mesh_cc.h) and the mesh cut down to the
+  largest one or to those above a size (``extract_mesh(keep_lcc=True)``, ``--keep_lcc``);
 * ``write_ply(path, mesh)``; ``python -m mli_nerf_amd.mesh`` is the command-line form.
 
 Differences from the reference, on purpose: the triangulation is this project's own table
 (mc_tables.py; the vertex set is any marching cubes'); vertices are welded across blocks; the
 sign convention is the project's (negative inside, triangles face outside; the reference negates
-the SDF for mcubes); no --keep_lcc (the reference applies it per block); blocks are not spread
-over ranks; vertex colours need an explicit light position (LumenRGB.forward needs pts_light,
-which the reference's extract_texture does not pass); the lattice includes the upper bound's
-plane (the reference's arange(min, max, intv) stops one step short of it).
+the SDF for mcubes); --keep_lcc keeps the largest component of the whole welded mesh, chosen by a
+fixed-point area with stated tie rules (the reference applies it to every block's unwelded piece
+on its own); blocks are not spread over ranks; vertex colours need an explicit light position
+(LumenRGB.forward needs pts_light, which the reference's extract_texture does not pass); the
+lattice includes the upper bound's plane (the reference's arange(min, max, intv) stops one step
+short of it).
 """
+import collections
 import math
 import sys
 import time
@@ -188,9 +194,156 @@ def vertex_attributes(model, verts, attributes=("normal",), light=None):
     return out
 
 
+# ---------------------------------------------------------------------------- connected components
+class Components(collections.namedtuple("Components", "label ids n_faces area area_q rounds")):
+    """label [V] int32 (the smallest vertex index of each vertex's component); ids [C] int64 the
+    labels that own >= 1 face, ascending; n_faces [C] int32; area [C] float64 (None without
+    vertices); area_q [C] int64 fixed-point area; rounds: labelling rounds run."""
+
+
+def cc_max_rounds(n_verts):
+    """The default round cap 2 * ceil(log2(max(V, 2))) + 8."""
+    return 2 * (max(int(n_verts), 2) - 1).bit_length() + 8
+
+
+def cc_workspace(n_verts, n_faces, max_rounds=None):
+    """Element counts of label (int32), changed (int32), comp_faces (int32) and comp_area + max_q
+    (int64) as connected_components allocates them (mli_cc_init_workspace gives the bytes)."""
+    if not (1 <= n_verts < 2 ** 31 and 0 <= n_faces < 2 ** 31):
+        raise ValueError("connected_components: 1 <= n_verts < 2^31 and 0 <= faces < 2^31 are needed, got %d and %d"
+                         % (n_verts, n_faces))
+    max_rounds = cc_max_rounds(n_verts) if max_rounds is None else int(max_rounds)
+    if not 1 <= max_rounds <= L.MESH_CC_MAX_ROUNDS:
+        raise ValueError("connected_components: max_rounds %d is outside 1 .. %d" % (max_rounds, L.MESH_CC_MAX_ROUNDS))
+    return n_verts, max_rounds, n_verts, n_verts + 1
+
+
+def area_unit(verts):
+    """(unit, 2^(44-e)) of the fixed-point face area: unit = 2^(e-44), e = ceil(log2(d2)), d2 the
+    squared diagonal of the vertices' bounding box in float64; (1, 1) when d2 = 0."""
+    ext = (verts.max(dim=0)[0].double() - verts.min(dim=0)[0].double()).tolist()
+    d2 = (ext[0] * ext[0] + ext[1] * ext[1]) + ext[2] * ext[2]
+    if not math.isfinite(d2):
+        raise ValueError("connected_components: the vertices are not finite")
+    if d2 == 0.0:
+        return 1.0, 1.0
+    m, e = math.frexp(d2)   # d2 = m * 2^e, 0.5 <= m < 1
+    if m == 0.5:
+        e -= 1
+    return math.ldexp(1.0, e - 44), math.ldexp(1.0, 44 - e)
+
+
+@torch.no_grad()
+def connected_components(faces, n_verts, verts=None, max_rounds=None, timings=None):
+    """Connected components of the graph whose vertices are 0 .. n_verts-1 and in which two
+    vertices are adjacent when a face names both (``faces`` [F,3] int64, a CUDA tensor).
+
+    Returns ``Components``.  A face belongs to the component of its first vertex.  With ``verts``
+    [V,3] f32 the components' areas are summed in fixed point (order-independent, the same bits
+    every run); without, area is None and area_q is 0.  Raises ValueError for an index outside
+    [0, n_verts) (checked before any launch) and RuntimeError when ``max_rounds`` rounds (default
+    cc_max_rounds) did not converge.  ``timings``: receives the seconds of 'labelling' and 'stats'."""
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int64 and faces.dim() == 2
+            and faces.shape[1] == 3):
+        raise ValueError("connected_components: faces must be a CUDA int64 tensor [F, 3]")
+    dev = faces.device
+    n_verts, F = int(n_verts), int(faces.shape[0])
+    n_label, n_changed, n_cf, n_area = cc_workspace(n_verts, F, max_rounds)
+    if verts is not None and not (torch.is_tensor(verts) and verts.device == dev and verts.dtype == torch.float32
+                                  and tuple(verts.shape) == (n_verts, 3)):
+        raise ValueError("connected_components: verts must be a float32 tensor [n_verts, 3] on the faces' device")
+    if F and not (int(faces.min()) >= 0 and int(faces.max()) < n_verts):
+        raise ValueError("connected_components: a face names a vertex outside 0 .. %d" % (n_verts - 1))
+    unit, inv_unit = area_unit(verts) if verts is not None else (1.0, 1.0)
+    clock = _Clock(timings, dev)
+    if F == 0:   # nothing to launch: every vertex is its own component and owns no face
+        empty = torch.empty(0, dtype=torch.int64, device=dev)
+        return Components(torch.arange(n_verts, dtype=torch.int32, device=dev), empty, empty.to(torch.int32),
+                          None if verts is None else empty.double(), empty, 0)
+    faces = faces.contiguous()
+    verts = None if verts is None else verts.contiguous()
+    label = torch.empty(n_label, dtype=torch.int32, device=dev)
+    changed = torch.empty(n_changed, dtype=torch.int32, device=dev)
+    comp_faces = torch.empty(n_cf, dtype=torch.int32, device=dev)
+    area_buf = torch.empty(n_area, dtype=torch.int64, device=dev)   # comp_area [V], then max_q
+    a = L.MeshCcArgs()
+    a.faces, a.n_faces, a.n_verts = L.ptr(faces), F, n_verts
+    a.verts = L.ptr(verts)
+    a.label, a.changed, a.max_rounds = L.ptr(label), L.ptr(changed), n_changed
+    a.comp_faces, a.comp_area, a.max_q = L.ptr(comp_faces), L.ptr(area_buf), L.ptr(area_buf[n_verts:])
+    a.inv_unit = inv_unit
+    with torch.cuda.device(dev):
+        L.call("mli_cc_init", a)
+        for r in range(n_changed):
+            a.round = r
+            L.call("mli_cc_round", a)
+            if not int(changed[r]):   # the round lowered nothing: the fixpoint
+                break
+        else:
+            raise RuntimeError("connected_components: no fixpoint after %d rounds (%d vertices, %d faces)"
+                               % (n_changed, n_verts, F))
+        clock.lap("labelling")
+        L.call("mli_cc_stats", a)
+        max_q, most = int(area_buf[n_verts]), int(comp_faces.max())
+    if max_q * most >= 2 ** 63:
+        raise ValueError("connected_components: the fixed-point area may overflow (largest face %d units, %d faces "
+                         "in one component)" % (max_q, most))
+    ids = torch.nonzero(comp_faces > 0).view(-1)
+    area_q = area_buf[:n_verts][ids]
+    out = Components(label, ids, comp_faces[ids], None if verts is None else area_q.double() * unit, area_q, r + 1)
+    clock.lap("stats")
+    return out
+
+
+def largest_component(ids, n_faces, area_q, by="area"):
+    """Position in ``ids`` of the largest component: the greatest area_q, then the most faces, then
+    the lowest label (``by='faces'``: the most faces, then the lowest label).  Host arrays."""
+    if by not in ("area", "faces"):
+        raise ValueError("filter_components: by=%r (known: 'area', 'faces')" % (by,))
+    ids, n_faces, area_q = (np.asarray(x, dtype=np.int64) for x in (ids, n_faces, area_q))
+    keys = (ids, -n_faces, -area_q) if by == "area" else (ids, -n_faces)
+    return int(np.lexsort(keys)[0])
+
+
+@torch.no_grad()
+def filter_components(mesh, keep="largest", by="area", min_faces=0, min_area=0.0, timings=None):
+    """A new ``Mesh`` with the components of ``mesh`` that have >= ``min_faces`` faces and an area
+    >= ``min_area``: all of them (``keep='all'``) or the largest (``keep='largest'``; see
+    largest_component for ``by`` and the tie rules).  Vertices no kept face names are dropped; the
+    order of vertices and faces is preserved; normals, colours, keys and face keys are carried."""
+    if keep not in ("largest", "all"):
+        raise ValueError("filter_components: keep=%r (known: 'largest', 'all')" % (keep,))
+    if by not in ("area", "faces"):
+        raise ValueError("filter_components: by=%r (known: 'area', 'faces')" % (by,))
+    verts, faces = mesh.verts, mesh.faces
+    dev = verts.device
+    V = verts.shape[0]
+    vkeep = torch.zeros(V, dtype=torch.bool, device=dev)
+    if V and faces.shape[0]:
+        cc = connected_components(faces, V, verts, timings=timings)
+        ok = (cc.n_faces >= int(min_faces)) & (cc.area >= float(min_area))
+        ids, n_f, a_q = (t[ok].cpu().numpy() for t in (cc.ids, cc.n_faces, cc.area_q))
+        if keep == "largest" and ids.size:
+            ids = ids[largest_component(ids, n_f, a_q, by):][:1]
+        kept = torch.zeros(V, dtype=torch.bool, device=dev)
+        kept[torch.from_numpy(ids).to(dev)] = True
+        vkeep = kept[cc.label.long()]
+    clock = _Clock(timings, dev)
+    fkeep = vkeep[faces[:, 0]] if faces.shape[0] else torch.zeros(0, dtype=torch.bool, device=dev)
+    remap = torch.cumsum(vkeep.to(torch.int64), 0) - 1
+
+    def rows(t, mask):
+        return None if t is None else t[mask]
+    out = Mesh(verts[vkeep], remap[faces[fkeep]], rows(mesh.normals, vkeep),
+               {n: c[vkeep] for n, c in mesh.colors.items()}, rows(mesh.keys, vkeep), rows(mesh.face_keys, fkeep))
+    clock.lap("compaction")
+    return out
+
+
 @torch.no_grad()
 def extract_mesh(model, resolution=512, block_res=256, bounds=None, attributes=("normal",), light=None,
-                 weld=True, sphere_filter=True, scale=1.0, center=(0.0, 0.0, 0.0), timings=None):
+                 weld=True, sphere_filter=True, scale=1.0, center=(0.0, 0.0, 0.0), timings=None,
+                 keep_lcc=False, min_component_faces=0):
     """The model's zero level set as a ``Mesh`` (device tensors).
 
     ``resolution``: lattice spacing 2 / resolution; ``bounds`` [[x0,x1],[y0,y1],[z0,z1]] (default:
@@ -198,8 +351,14 @@ def extract_mesh(model, resolution=512, block_res=256, bounds=None, attributes=(
     (the result does not depend on it); ``weld``: one vertex per lattice edge across blocks,
     vertices sorted by key and faces by face key; ``sphere_filter``: for a sphere-bounded scene drop
     vertices with |v| >= 1 and the faces touching them; ``scale`` / ``center``: v * scale + center,
-    applied last.  ``timings``: a dict that receives the seconds spent per phase (synchronises)."""
+    applied last.  ``timings``: a dict that receives the seconds spent per phase (synchronises).
+    ``keep_lcc``: keep only the largest connected component (filter_components: by area, then
+    faces, then lowest label); ``min_component_faces``: drop the components with fewer faces.
+    Both act on the welded, sphere-filtered mesh, before the attributes are evaluated."""
     attributes = _check_attributes(model, attributes, light)
+    if (keep_lcc or min_component_faces) and not weld:
+        raise ValueError("extract_mesh: keep_lcc / min_component_faces need weld=True (the blocks' copies of a "
+                         "shared vertex would split every component along the block planes)")
     model.eval()
     model.prepare()   # the engine as trained: active_levels, tap epsilon, weights
     eng = model.engine
@@ -253,7 +412,13 @@ def extract_mesh(model, resolution=512, block_res=256, bounds=None, attributes=(
         verts, keys = verts[keep], keys[keep]
         faces, fkeys = remap[faces[fkeep]], fkeys[fkeep]
     clock.lap("stitch")
-    attrs = vertex_attributes(model, verts, attributes, light) if verts.shape[0] else \
+    if (keep_lcc or min_component_faces) and verts.shape[0]:
+        # filter_largest_cc (mesh.py:151-158), on the whole welded mesh
+        kept = filter_components(Mesh(verts, faces, keys=keys, face_keys=fkeys), keep="largest" if keep_lcc else "all",
+                                 min_faces=min_component_faces)
+        verts, faces, keys, fkeys = kept.verts, kept.faces, kept.keys, kept.face_keys
+        clock.lap("components")
+    attrs =vertex_attributes(model, verts, attributes, light) if verts.shape[0] else \
         {n: torch.empty(0, 3, device=dev) for n in attributes}
     clock.lap("attributes")
     normals = attrs.pop("normal", None)
@@ -325,8 +490,9 @@ def write_ply(path, mesh):
 # ---------------------------------------------------------------------------- command line
 def main(argv=None):
     """extract_mesh.py's flags: --config --checkpoint --resolution --block_res --output_file;
-    --textured becomes --attributes normal,reflectance --light x,y,z; no --keep_lcc.  --config is
-    a YAML path or the name of a built-in preset; --a.b.c=v overrides follow."""
+    --textured becomes --attributes normal,reflectance --light x,y,z; --keep_lcc keeps the largest
+    component of the whole mesh, --min_component_faces N drops the smaller ones.  --config is a
+    YAML path or the name of a built-in preset; --a.b.c=v overrides follow."""
     import argparse
     import os
     from .trainer import Trainer
@@ -340,6 +506,8 @@ def main(argv=None):
     ap.add_argument("--light", default=None, help="world-space light position x,y,z (for colours)")
     ap.add_argument("--scale", type=float, default=1.0, help="sphere_radius of the scene's annotation")
     ap.add_argument("--center", default="0,0,0", help="sphere_center of the scene's annotation")
+    ap.add_argument("--keep_lcc", action="store_true", help="keep only the largest connected component")
+    ap.add_argument("--min_component_faces", type=int, default=0, help="drop components with fewer faces")
     args, cfg_cmd = ap.parse_known_args(argv)
     from . import configs
     from .config import load_config, parse_overrides
@@ -359,7 +527,8 @@ def main(argv=None):
     attributes = tuple(a for a in args.attributes.split(",") if a)
     light = None if args.light is None else tuple(float(x) for x in args.light.split(","))
     mesh = extract_mesh(trainer.model, resolution=args.resolution, block_res=args.block_res, attributes=attributes,
-                        light=light, scale=args.scale, center=tuple(float(x) for x in args.center.split(",")))
+                        light=light, scale=args.scale, center=tuple(float(x) for x in args.center.split(",")),
+                        keep_lcc=args.keep_lcc, min_component_faces=args.min_component_faces)
     out_dir = os.path.dirname(args.output_file)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)

@@ -2,12 +2,15 @@
 
   python tools/mesh_profile.py --resolution 512 --block_res 128 --out profiles/mesh/res512_block128.json
   python tools/mesh_profile.py --oracle --out profiles/mesh/oracle_cpu.json      (CPU, for scale)
+  python tools/mesh_profile.py --block_res 256 --keep_lcc --out profiles/mesh/res512_block256_lcc.json
 
 Phases (host wall clock with a device synchronisation after each, mesh._Clock): lattice_sdf (the
 mli_sdf SDF-mode calls and their inputs), marching_cubes (count, the size read-back, emit),
 stitch (concatenate, weld, sort, filter), attributes (FIELD + heads at the vertices).  The
 marching-cubes launches are also timed with device events (_lib.PROFILE), which leaves out the
-read-back: achieved bytes/s = passes * 4 B * lattice points / that time.
+read-back: achieved bytes/s = passes * 4 B * lattice points / that time.  --keep_lcc: the run
+with and without the connected-component filter in turn, the phase "components" split into
+labelling / stats / compaction, the rounds used, and scipy on the host for scale.
 """
 import argparse
 import json
@@ -53,6 +56,8 @@ def gpu_record(args):
     model = model.to("cuda:0")
     kw = dict(resolution=args.resolution, block_res=args.block_res, attributes=("normal", "reflectance"),
               light=(1.5, -2.0, 2.5))
+    if args.keep_lcc:
+        return lcc_record(args, model, kw)
     extract_mesh(model, **kw)   # warm-up: allocations, first launches
     runs = []
     for _ in range(args.repeats):
@@ -92,6 +97,73 @@ def gpu_record(args):
                 sdf_points_per_second=points / dev["mli_sdf:sdf"] if dev.get("mli_sdf:sdf") else None)
 
 
+def _timed(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t
+
+
+def lcc_record(args, model, kw):
+    """extract_mesh with and without keep_lcc in turn (the same process, the same warm state), the
+    components phase split into labelling / stats / compaction on the unfiltered mesh, the device
+    time of its launches, and scipy's connected_components on the host for scale."""
+    from mli_nerf_amd import _lib as L
+    from mli_nerf_amd.mesh import Mesh, cc_max_rounds, connected_components, extract_mesh, filter_components
+    extract_mesh(model, keep_lcc=True, **kw)   # warm-up: allocations, first launches
+    runs = {False: [], True: []}
+    for _ in range(args.repeats):
+        for flag in (False, True):
+            timings = {}
+            mesh, dt = _timed(lambda: extract_mesh(model, timings=timings, keep_lcc=flag, **kw))
+            timings["total"] = dt
+            runs[flag].append(timings)
+            if flag:
+                kept = (int(mesh.verts.shape[0]), int(mesh.faces.shape[0]))
+    best = {flag: min(r, key=lambda t: t["total"]) for flag, r in runs.items()}
+    full = extract_mesh(model, **dict(kw, attributes=()))
+    bare = Mesh(full.verts, full.faces, keys=full.keys, face_keys=full.face_keys)
+    splits = []
+    for _ in range(args.repeats):
+        split = {}
+        filter_components(bare, timings=split)
+        splits.append(split)
+    split = min(splits, key=lambda s: sum(s.values()))
+    L.PROFILE, L.PROFILE_NAMES = [], set(L.MESH_CC_ENTRY_POINTS)
+    cc = connected_components(full.faces, full.verts.shape[0], full.verts)
+    torch.cuda.synchronize()
+    dev = {}
+    for name, e0, e1 in L.PROFILE:
+        dev[name] = dev.get(name, 0.0) + e0.elapsed_time(e1) * 1e-3
+    L.PROFILE = L.PROFILE_NAMES = None
+    host = None
+    try:
+        import numpy as np
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components as scipy_cc
+        t = time.perf_counter()
+        f = full.faces.cpu().numpy()
+        rows, cols = np.concatenate([f[:, 0], f[:, 1], f[:, 2]]), np.concatenate([f[:, 1], f[:, 2], f[:, 0]])
+        n_host, _ = scipy_cc(coo_matrix((np.ones(rows.size, dtype=np.int8), (rows, cols)),
+                                        shape=(full.verts.shape[0],) * 2), directed=False)
+        host = dict(seconds=time.perf_counter() - t, components=int(n_host),
+                    note="scipy.sparse.csgraph.connected_components on the host, the copy of the faces included; "
+                         "labels only, no areas; for scale")
+    except ImportError:
+        pass
+    n = args.resolution + 1
+    comp = best[True].get("components", 0.0)
+    return dict(what="extract_mesh(keep_lcc=True)", device=torch.cuda.get_device_name(0), log2T=args.log2T,
+                resolution=args.resolution, lattice=[n, n, n], block_res=args.block_res,
+                vertices=int(full.verts.shape[0]), faces=int(full.faces.shape[0]), components=int(cc.ids.numel()),
+                vertices_kept=kept[0], faces_kept=kept[1], rounds=cc.rounds,
+                max_rounds=cc_max_rounds(int(full.verts.shape[0])),
+                runs_plain=runs[False], runs_keep_lcc=runs[True], best_plain=best[False], best_keep_lcc=best[True],
+                components_seconds=comp, components_share_of_total=comp / best[True]["total"],
+                components_split_seconds=split, device_seconds=dev, host_scipy=host)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--resolution", type=int, default=512)
@@ -99,6 +171,7 @@ def main():
     ap.add_argument("--log2T", type=int, default=22)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--oracle", action="store_true")
+    ap.add_argument("--keep_lcc", action="store_true", help="profile the connected-component filter")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     rec = oracle_record(args.log2T) if args.oracle else gpu_record(args)
