@@ -979,9 +979,14 @@ __global__ __launch_bounds__(256) void hash_bwd_kernel(mli_hash_bwd_args a) {
     const int c0 = lane & 31;
     auto run_scatter = [&](const uint32_t (&cellk)[3], float (&V)[8][8], bool mine) MLI_LAMBDA_FI {
       // lanes without a contribution get a lane-unique key: singleton runs that never scatter
-      // and never lengthen the scan
+      // and never lengthen the scan.  The key alone does not keep them apart from a contributing
+      // neighbour -- (-1, lane, -1) is the cell of a point just below the grid -- so a run also
+      // ends wherever `mine` changes (joined to such a neighbour, the idle lane became the run's
+      // tail and scattered the total to its own cell).
       const uint32_t key[3] = {mine ? cellk[0] : 0xFFFFFFFFu, mine ? cellk[1] : (uint32_t)lane,
                                mine ? cellk[2] : 0xFFFFFFFFu};
+      const uint64_t bal = __ballot(mine);
+      const bool prev_mine = (((bal << 1) >> lane) & 1ull) != 0, next_mine = (((bal >> lane) >> 1) & 1ull) != 0;
 #if MLI_HB_DPP
       // neighbour keys by DPP wave_shr:1 / wave_shl:1 (lane 0 / 63 read 0: c0 == 0 / 31 decide)
       const uint32_t px = dpp_u32<0x138, 0xF>(key[0]), py = dpp_u32<0x138, 0xF>(key[1]),
@@ -989,7 +994,7 @@ __global__ __launch_bounds__(256) void hash_bwd_kernel(mli_hash_bwd_args a) {
 #else
       const uint32_t px = __shfl_up(key[0], 1), py = __shfl_up(key[1], 1), pz = __shfl_up(key[2], 1);
 #endif
-      const bool head = c0 == 0 || px != key[0] || py != key[1] || pz != key[2];
+      const bool head = c0 == 0 || px != key[0] || py != key[1] || pz != key[2] || prev_mine != mine;
       int start = head ? c0 : 0;  // first lane of this lane's run: max-scan of the heads
 #if MLI_HB_DPP
       // (max is exact: the same values as the bpermute scan) in-row row_shr steps, then rows 1 / 3
@@ -1008,7 +1013,6 @@ __global__ __launch_bounds__(256) void hash_bwd_kernel(mli_hash_bwd_args a) {
       }
 #endif
       // any lane of the run contributing (runs without contributions issue nothing)
-      const uint64_t bal = __ballot(mine);
       const uint32_t hb = (uint32_t)(bal >> (32 * h));
       const uint32_t upto = c0 == 31 ? 0xFFFFFFFFu : ((2u << c0) - 1u);
       const uint32_t from = ~((1u << start) - 1u);
@@ -1059,7 +1063,7 @@ __global__ __launch_bounds__(256) void hash_bwd_kernel(mli_hash_bwd_args a) {
 #else
       const uint32_t nx = __shfl_down(key[0], 1), ny = __shfl_down(key[1], 1), nz = __shfl_down(key[2], 1);
 #endif
-      const bool tail = (c0 == 31 || nx != key[0] || ny != key[1] || nz != key[2]) && any;
+      const bool tail = (c0 == 31 || nx != key[0] || ny != key[1] || nz != key[2] || next_mine != mine) && any;
       // Coalesced scatter: the run totals go through LDS so one atomic instruction adds one
       // run's 8 corners x 8 features with 8 consecutive lanes per corner (one 32 B L2 request
       // per corner instead of 8 -- atomics here are request-rate bound, tools/atomic_bench.hip)
