@@ -450,7 +450,8 @@ def test_fused_tail_matches_three_calls(case, R):
     assert f1["losses"] == f2["losses"] and torch.equal(f1["grad"], f2["grad"])
 
 
-@pytest.mark.parametrize("R,N,intr", [(151, 37, True), (5, 128, True), (1024, 64, False)])
+@pytest.mark.parametrize("R,N,intr", [(151, 37, True), (5, 128, True), (1024, 64, False), (37, 255, True),
+                                      (6, 129, False)])
 def test_composite_loss_kernel_ragged(R, N, intr):
     """mli_composite_loss against the three calls through the C ABI on random inputs of shapes
     the trainer never produces: R not a multiple of the 4 rays per workgroup, N not a multiple of

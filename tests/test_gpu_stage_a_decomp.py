@@ -9,6 +9,10 @@ per tensor cosine >= 0.995 and relative error <= 10 % (measured up to 4 %).  Two
     operands -- the stored fragment images (layout.unfrag), the weights rounded to fp16 as the
     pack kernels round them, the fp32 vectors the previous kernel wrote -- and compared with
     what that kernel made of them:
+      * mli_composite_bwd_geo: d sdf, d grad, the rgb rows of dZ4 and d s_var by float64 autograd
+        through tests/rays_ref.py's composite of the GPU's dists, sdf, gradients, head outputs
+        and d rgb (d s_var at the bar of tests/test_gpu_rays.py: 8 x the fp32 oracle's own error
+        against float64, not the end-to-end 2 %);
       * the head (mli_rgb_fwd, mli_geo_bwd's dX chain): X_{l+1} = relu(W_l X_l + b_l) and
         dZ_l = mask_l (W_{l+1}^T dZ_{l+1}), each from the GPU's own input image;
       * mli_geo_bwd's geometry tail: d normal = (W0^T dZ0)[normal rows] (fp32),
@@ -40,6 +44,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import rays_cases
+import rays_ref
 from margins import RECORDS, _test_id, check
 from mli_nerf_amd import layout, synthetic
 from mli_nerf_amd.configs import preset
@@ -132,6 +138,27 @@ def test_stage_a_gradient_error_decomposition(R, Nc, Nf, it):
     def chk(key, name, val, bar, op="<="):
         worst[key] = max(worst.get(key, 0.0), val) if op == "<=" else min(worst.get(key, 1.0), val)
         check(name, val, bar, op)
+
+    # ------------------------------------------------------------ leg (b): mli_composite_bwd_geo
+    anneal = float(np.float32(min(model.progress / eng.cfg.anneal_end, 1.0)))
+    white = 1 if eng.cfg.white_bg else 0
+    f32 = lambda t, *shape: t.detach().float().cpu().reshape(-1)[:int(np.prod(shape))].reshape(*shape)   # noqa: E731
+    geo_in = dict(R=R, N=N, dists=f32(dists, N, R), far=f32(rays["far"], R), ray_unit=f32(rays["ray_unit"], R, 3),
+                  ray_norm=torch.ones(R), sdf=f32(fld["sdf"], N, R), grad=f32(fld["grad"], N, R, 3),
+                  y=f32(hd["y"], N, R, 8), d_rgb=f32(B["d_rgb"], R, 3))
+    s_var_gpu = model.s_var.detach().float().cpu().reshape(1)
+    geo = rays_ref.composite_bwd_geo(geo_in["dists"], geo_in["far"], geo_in["ray_unit"], geo_in["sdf"], geo_in["grad"],
+                                     geo_in["y"], s_var_gpu, anneal, white, geo_in["d_rgb"], scale)
+    chk("fp32 out", "stage-a composite_bwd_geo d_sdf", rays_cases.err(f32(B["d_sdf"], N, R), geo["d_sdf"]), 1e-4)
+    chk("fp32 out", "stage-a composite_bwd_geo d_grad", rays_cases.err(f32(B["d_grad"], N, R, 3), geo["d_grad"]), 1e-4)
+    chk("fp32 out", "stage-a composite_bwd_geo dz4", rays_cases.err(f32(B["dz4"], N, R, 8), geo["dz4"]), 1e-4)
+    # d s_var: 8 x the fp32 oracle's error against float64, the larger of this batch's and the
+    # largest over the case list of tests/test_gpu_rays.py (one number per case: a single case's
+    # oracle error can be small by accident), floor 1e-6
+    o_geo = rays_cases.oracle_composite(geo_in, float(s_var_gpu[0]), anneal, white, grads=True)
+    e_svar = max(rays_cases.err(o_geo["d_s_var"], geo["d_s_var"]), rays_cases.d_s_var_oracle_err())
+    chk("s_var", "stage-a composite_bwd_geo d_s_var", rays_cases.err(gpu_grad("s_var").reshape(1), geo["d_s_var"]),
+        max(8.0 * e_svar, 1e-6))
 
     # ------------------------------------------------------------ leg (b): the head
     head = layout.HEADS_A[0][0]
