@@ -199,6 +199,14 @@ typedef struct {
    * head.  Segments past the workgroup's last ray are not written. */
   const float* weights;   /* [N][R] composite weights of this render (mli_composite_fwd, y = NULL) */
   float* q4;              /* [S/256][MLI_Q4_SEGS(N)][n_heads][257][4] fp32 */
+  /* Live rays, optional (both NULL: dense): only the live rays of mli_live_rays are processed (PQ
+   * mode, 256 % N == 0).  The grid stays S / 256; workgroup b works on the compact tiles
+   * 8 b .. 8 b + 7 and returns at once when 8 b >= *n_live_tiles.  Wave w's samples are the
+   * original tile tile_list[8 b + w] (rays, dists, grad, h0, weights, y, the q4 slot of its ray);
+   * the images the weight gradients read (feat_frag, xT, masks) are written at the compact tile
+   * 8 b + w, dense from tile 0 on. */
+  const int32_t* tile_list;
+  const int32_t* n_live_tiles;
 } mli_rgb_fwd_args;
 #define MLI_Q4_SCALE 65536.0f
 /* ray segments per 256-sample workgroup (an upper bound; N % 32 == 0) */
@@ -258,6 +266,10 @@ typedef struct {
   int skip_dz3;           /* ABI 18: 1 = the dZ3 images (layer 3 of every head) are not stored and
                              their part of dzT is left untouched: mli_wgrad rebuilds them
                              (mli_wgrad_job.rb_*)                                              */
+  /* Live rays, optional (both NULL: dense), as mli_rgb_fwd_args: dz4 is read at the original tile
+   * tile_list[8 b + w]; masks are read and dzT is written at the compact tile 8 b + w. */
+  const int32_t* tile_list;
+  const int32_t* n_live_tiles;
 } mli_rgb_bwd_args;
 int mli_rgb_bwd(const mli_rgb_bwd_args* a, mli_stream_t s);
 /* bytes[0..1]: dzT, dz4T. */
@@ -315,6 +327,15 @@ typedef struct {
   int classes;            /* MLI_WGRAD_* mask */
   int deterministic;      /* 0: fp32 atomics; 1: slice partials + ordered reduction */
   float* workspace;       /* deterministic: mli_wgrad_workspace bytes (reused across classes) */
+  /* Live rays, optional (both NULL: dense), fragment-image jobs only: the operand images hold the
+   * live tiles of mli_live_rays in compact order.  The k-slices still partition the ORIGINAL S
+   * (the same k_split / n_split); the slice [k0, k1) streams the compact tiles
+   * [tile_rank[k0 / 32], tile_rank[k1 / 32]) -- the tiles it skips are all zero in the dense
+   * images, so every sum keeps its partition and order.  A rebuild job reads the dz4 rows of
+   * compact tile t at the original tile tile_list[t], its mask at t.  A slice without a live tile
+   * issues no DMA (deterministic: it writes a zero slab). */
+  const int32_t* tile_rank; /* [S/32 + 1] */
+  const int32_t* tile_list; /* [S/32] */
 } mli_wgrad_args;
 int mli_wgrad(const mli_wgrad_args* a, mli_stream_t s);
 /* bytes[0]: workspace (0 unless deterministic): the largest class in `classes`. */
@@ -335,10 +356,38 @@ typedef struct {
   float* db[3];           /* per head: [k_out] */
   int k_out[3];           /* 3, 3, 1 (LumenRGB 'rgb_r_s') */
   float* workspace;       /* bytes[0] */
+  const int32_t* tile_rank; /* live rays, optional (NULL: dense): [S/32 + 1] of mli_live_rays; the
+                             (workgroup, segment) items of rays without a live tile are skipped (their
+                             q4 slots were not written) */
 } mli_dw4_args;
 int mli_dw4(const mli_dw4_args* a, mli_stream_t s);
 /* bytes[0]: workspace (slice partials). */
 int mli_dw4_workspace(const mli_dw4_args* a, int64_t* bytes);
+
+/* ---------------------------------------------------------------- live rays
+ * A ray is live when at least one of its N composite weights is not exactly 0.0.  A dead ray's
+ * head outputs are multiplied by exact zeros everywhere (w_s y_s, dz4 = D w_s y (1 - y), its dW /
+ * db / q4 terms), so the heads, their backward and the weight gradients may skip it.  Writes the
+ * compaction the other ops take (T = N / 32 tiles per ray, G = 256 / N rays per workgroup, L live
+ * rays, all int32):
+ *   tile_list [S/32]     compact position -> original tile r T + j: the live rays in ascending
+ *                        order, then the dead rays in ascending order (a permutation); the first
+ *                        (-L mod G) dead rays pad the last workgroup and are processed like live ones
+ *   tile_rank [S/32 + 1] live tiles before each original tile (pad rays are not counted);
+ *                        tile_rank[S/32] = L T
+ *   n_live_tiles         ceil(L / G) G T, a multiple of 8
+ * and zeroes the y rows of every dead ray (mli_composite_loss reads y of every sample; the pad
+ * rays' rows are rewritten by mli_rgb_fwd).  256 % N == 0, R % G == 0.  Two launches: a per-ray
+ * flag pass over the weights, then one workgroup's scan over the R flags (no atomics). */
+struct mli_live_rays_args_s {
+  int R, N;
+  const float* weights;   /* [N][R] */
+  float* y;               /* [N][R][8] or NULL */
+  int32_t* flags;         /* scratch [R] */
+  int32_t* tile_list; int32_t* tile_rank; int32_t* n_live_tiles;
+};
+typedef struct mli_live_rays_args_s mli_live_rays_args;
+int mli_live_rays(const mli_live_rays_args* a, mli_stream_t s);
 
 /* ---------------------------------------------------------------- stage a (geometry training)
  * Backward of the whole render w.r.t. the geometry: replaces autograd through

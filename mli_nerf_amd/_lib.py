@@ -51,7 +51,8 @@ class SampleFineArgs(C.Structure):
 class RgbFwdArgs(C.Structure):
     _fields_ = [("R", I32), ("N", I32), ("center", P), ("ray_unit", P), ("pts_light", P),
                 ("dists", P), ("grad", P), ("h0", P), ("wfwd", P), ("y", P), ("feat_frag", P),
-                ("xT", P), ("masks", P), ("n_heads", I32), ("weights", P), ("q4", P)]
+                ("xT", P), ("masks", P), ("n_heads", I32), ("weights", P), ("q4", P),
+                ("tile_list", P), ("n_live_tiles", P)]
 
 
 class CompositeArgs(C.Structure):
@@ -69,7 +70,7 @@ class CompositeBwdArgs(C.Structure):
 
 class RgbBwdArgs(C.Structure):
     _fields_ = [("R", I32), ("N", I32), ("dz4", P), ("wbwd", P), ("masks", P), ("dzT", P),
-                ("dz4T", P), ("skip_dz3", I32)]
+                ("dz4T", P), ("skip_dz3", I32), ("tile_list", P), ("n_live_tiles", P)]
 
 
 class WgradJob(C.Structure):
@@ -92,12 +93,18 @@ def frag_job(a, b, M, K, dw, db, ldw, a_kst, b_kst, order=FRAG_ACC, b_order=None
 
 class WgradArgs(C.Structure):
     _fields_ = [("S", I32), ("n_jobs", I32), ("jobs", P), ("classes", I32), ("deterministic", I32),
-                ("workspace", P)]
+                ("workspace", P), ("tile_rank", P), ("tile_list", P)]
 
 
 class Dw4Args(C.Structure):
     _fields_ = [("R", I32), ("N", I32), ("n_heads", I32), ("q4", P), ("dray", P), ("scale", F32),
-                ("dw", P * 3), ("db", P * 3), ("k_out", I32 * 3), ("workspace", P)]
+                ("dw", P * 3), ("db", P * 3), ("k_out", I32 * 3), ("workspace", P),
+                ("tile_rank", P)]
+
+
+class LiveRaysArgs(C.Structure):
+    _fields_ = [("R", I32), ("N", I32), ("weights", P), ("y", P), ("flags", P), ("tile_list", P),
+                ("tile_rank", P), ("n_live_tiles", P)]
 
 
 Q4_SCALE = 65536.0  # include/mli_hip.h MLI_Q4_SCALE
@@ -209,7 +216,7 @@ ENTRY_POINTS = {
     "mli_sample_coarse": SampleCoarseArgs, "mli_sample_fine": SampleFineArgs,
     "mli_rgb_fwd": RgbFwdArgs, "mli_composite_fwd": CompositeArgs,
     "mli_composite_bwd": CompositeBwdArgs, "mli_rgb_bwd": RgbBwdArgs,
-    "mli_wgrad": WgradArgs, "mli_dw4": Dw4Args,
+    "mli_wgrad": WgradArgs, "mli_dw4": Dw4Args, "mli_live_rays": LiveRaysArgs,
     "mli_pack": PackArgs, "mli_pack_sdf": PackSdfArgs, "mli_grad_assemble": AssembleArgs,
     "mli_adamw": AdamwArgs, "mli_cast_f16": CastArgs, "mli_stage_b_loss": LossArgs,
     "mli_composite_bwd_geo": CompositeBwdGeoArgs, "mli_geo_bwd": GeoBwdArgs, "mli_sdf_bwd": SdfBwdArgs,

@@ -486,14 +486,20 @@ MLI_FI void q4_tile(const mli_rgb_fwd_args& a, uint8_t* lds, const half8 (&X)[19
     const int segs = MLI_Q4_SEGS(N);
     const int nthr = ROLE == STORE ? G::THREADS / 2 : G::THREADS;
     const int tid = ROLE == STORE ? threadIdx.x - G::THREADS / 2 : threadIdx.x;
-    f32x4* qo = reinterpret_cast<f32x4*>(a.q4) + (size_t)blockIdx.x * segs * a.n_heads * 257;
+    f32x4* qb = reinterpret_cast<f32x4*>(a.q4);
     for (int it = tid; it < nseg * 257; it += nthr) {
       const int seg = it / 257, row = it - seg * 257;
+      // the segment's q4 item: [wg][seg] of the dense order; live rays (tile_list, 256 % N == 0: the
+      // workgroup holds whole rays, segs per workgroup = rays per workgroup): the item of the
+      // segment's original ray, [r / G][r % G] = r
+      size_t item = (size_t)blockIdx.x * segs + seg;
+      if (a.tile_list) item = (size_t)(a.tile_list[t0 + seg * (N / 32)] * 32 / N);
+      f32x4* qo = qb + item * a.n_heads * 257;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int w = 0; w < G::NW; ++w)
         if ((t0 + w) * 32 / N - r_first == seg) v += *reinterpret_cast<const f32x4*>(q4_park(w) + row * 16);
-      gstore_nt(qo + ((size_t)seg * a.n_heads + hd) * 257 + row, v);
+      gstore_nt(qo + (size_t)hd * 257 + row, v);
     }
   }
   block_sync();  // the Q park is free again
@@ -509,8 +515,12 @@ MLI_FI void rgb_fwd_body(const mli_rgb_fwd_args& a, uint8_t* lds) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
   const int S = a.R * a.N;
+  // `tile`: the wave's position in the images the weight gradients read (x0, X1..X3, masks);
+  // `tile_o`: the 32 samples it works on -- the same tile, or (live rays: tile_list) the original
+  // tile tile_list[tile]: rays, dists, grad, h0, weights, y and the q4 item go by it
   const int tile = blockIdx.x * G::NW + wave;
-  const int m = tile * 32 + c;
+  const int tile_o = (PQ && a.tile_list) ? __builtin_amdgcn_readfirstlane(a.tile_list[tile]) : tile;
+  const int m = tile_o * 32 + c;
   const int r = m / a.N, k = m - r * a.N;
   const size_t slot = (size_t)k * a.R + r;
   auto bytes = [](int cc) MLI_LAMBDA_FI { return fwd_bytes(cc); };
@@ -528,7 +538,7 @@ MLI_FI void rgb_fwd_body(const mli_rgb_fwd_args& a, uint8_t* lds) {
   // gload16 -- with the extras stores pending the compiler waited vmcnt(0) for them inside the
   // feat layer, draining its first weight DMAs)
   {
-    const half8* src = reinterpret_cast<const half8*>(a.h0 + (size_t)tile * FRAG_TILE) + lane;
+    const half8* src = reinterpret_cast<const half8*>(a.h0 + (size_t)tile_o * FRAG_TILE) + lane;
 #pragma unroll
     for (int q = 0; q < 16; ++q) B[q] = gload16(src + q * 64);
   }
@@ -728,6 +738,8 @@ template <bool TRAIN, bool PQ>
 __global__ __launch_bounds__(GFwd::THREADS) void rgb_fwd_kernel(mli_rgb_fwd_args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   typedef typename std::conditional<TRAIN, GFwdT, GFwd>::type G;
+  // live rays: a workgroup past the live tiles returns before any DMA or barrier
+  if (PQ && a.n_live_tiles && (int)(blockIdx.x * G::NW) >= *a.n_live_tiles) return;
   if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= G::NW / 2) rgb_fwd_body<G, TRAIN, PQ, STORE>(a, lds);
   else rgb_fwd_body<G, TRAIN, PQ, DMA>(a, lds);
 }
@@ -745,8 +757,11 @@ MLI_FI void rgb_bwd_body(const mli_rgb_bwd_args& a, uint8_t* lds) {
   const int c = lane & 31, h = lane >> 5;
   const int S = a.R * a.N;
   const int tiles = S / 32;
+  // (tile: the position in the masks / dZ images; tile_o: the original tile, for dz4 -- as
+  // rgb_fwd_body)
   const int tile = blockIdx.x * G::NW + wave;
-  const int m = tile * 32 + c;
+  const int tile_o = a.tile_list ? __builtin_amdgcn_readfirstlane(a.tile_list[tile]) : tile;
+  const int m = tile_o * 32 + c;
   const int r = m / a.N, k = m - r * a.N;
   const size_t slot = (size_t)k * a.R + r;
   auto bytes = [](int cc) MLI_LAMBDA_FI { return bwd_bytes(cc); };

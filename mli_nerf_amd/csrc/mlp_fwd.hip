@@ -11,6 +11,9 @@ extern "C" int mli_rgb_fwd(const mli_rgb_fwd_args* a, mli_stream_t s) {
   const bool pq = a->weights != nullptr;
   if (pq && (!train || a->q4 == nullptr || a->N % 32 != 0)) return (int)hipErrorInvalidValue;
   if (!pq && a->q4 != nullptr) return (int)hipErrorInvalidValue;
+  // live rays: PQ mode only, both arrays or none, a workgroup holds whole rays
+  if ((a->tile_list != nullptr) != (a->n_live_tiles != nullptr)) return (int)hipErrorInvalidValue;
+  if (a->tile_list && (!pq || 256 % a->N != 0)) return (int)hipErrorInvalidValue;
   const dim3 grid(S / GFwd::SAMPLES), block(GFwd::THREADS);
   if (pq) return mli_launch_rgb_fwd_pq(a, (hipStream_t)s);
   if (train) return mli_launch_rgb_fwd_train(a, (hipStream_t)s);

@@ -825,3 +825,86 @@ extern "C" int mli_composite_loss_workspace(const mli_composite_loss_args* a, in
   bytes[1] = (int64_t)R * a->comp.N * 8 * 4;                            // dz4
   return 0;
 }
+
+// ---------------------------------------------------------------------- live rays
+// mli_live_rays: which rays the heads must process.  A ray all of whose composite weights are
+// exactly 0.0 (it misses the bounding sphere: sdf = outside_val saturates both NeuS sigmoids; or
+// free space with sdf * inv_s > 17) multiplies its head outputs by exact zeros in the composite,
+// in dz4 and in every dW / db / q4 term.  Pass 1 (64 rays per workgroup, four lanes per ray over
+// the samples k = j, j + 4, ...): flags[r] = any weight != 0, and the y rows of a dead ray are
+// zeroed (mli_composite_loss reads y of every sample).  Pass 2 (one workgroup): an exclusive scan
+// of the flags in ray order and the lists (include/mli_hip.h, mli_live_rays_args).
+namespace {
+
+constexpr int LR_RAYS = 64, LR_SCAN = 1024;
+
+__global__ __launch_bounds__(4 * LR_RAYS) void live_flags_kernel(mli_live_rays_args a) {
+  __shared__ int any[4][LR_RAYS];
+  const int rl = threadIdx.x % LR_RAYS, j = threadIdx.x / LR_RAYS;
+  const int r = blockIdx.x * LR_RAYS + rl;
+  int live = 0;
+  if (r < a.R)
+    // (on the bit pattern: +-0.0 dead, denormals and NaN live, whatever the denormal mode)
+    for (int k = j; k < a.N; k += 4)
+      live |= (__builtin_bit_cast(uint32_t, a.weights[(size_t)k * a.R + r]) & 0x7fffffffu) != 0;
+  any[j][rl] = live;
+  __syncthreads();
+  live = any[0][rl] | any[1][rl] | any[2][rl] | any[3][rl];
+  if (r >= a.R) return;
+  if (j == 0) a.flags[r] = live;
+  if (!live && a.y != nullptr) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    for (int k = j; k < a.N; k += 4) {
+      f32x4* row = reinterpret_cast<f32x4*>(a.y + ((size_t)k * a.R + r) * 8);
+      row[0] = z;
+      row[1] = z;
+    }
+  }
+}
+
+__global__ __launch_bounds__(LR_SCAN) void live_scan_kernel(mli_live_rays_args a) {
+  __shared__ int sums[LR_SCAN];
+  const int t = threadIdx.x;
+  const int T = a.N / 32, G = 256 / a.N;
+  // thread t: rays [r0, r1), a contiguous chunk in ray order
+  const int per = (a.R + LR_SCAN - 1) / LR_SCAN;
+  const int r0 = min(t * per, a.R), r1 = min(r0 + per, a.R);
+  int cnt = 0;
+  for (int r = r0; r < r1; ++r) cnt += a.flags[r];
+  sums[t] = cnt;
+  __syncthreads();
+  // inclusive scan (Hillis-Steele; integer sums: any order gives the same counts)
+  for (int o = 1; o < LR_SCAN; o <<= 1) {
+    const int v = t >= o ? sums[t - o] : 0;
+    __syncthreads();
+    sums[t] += v;
+    __syncthreads();
+  }
+  const int L = sums[LR_SCAN - 1];
+  int before = sums[t] - cnt;  // live rays before ray r0
+  for (int r = r0; r < r1; ++r) {
+    const int live = a.flags[r];
+    // compact ray position: the live rays first, then the dead ones, each in ascending order
+    const int pos = live ? before : L + (r - before);
+    for (int i = 0; i < T; ++i) {
+      a.tile_list[pos * T + i] = r * T + i;
+      a.tile_rank[r * T + i] = before * T + (live ? i : 0);
+    }
+    before += live;
+  }
+  if (t == 0) {
+    a.tile_rank[a.R * T] = L * T;
+    a.n_live_tiles[0] = (L + G - 1) / G * G * T;
+  }
+}
+
+}  // namespace
+
+extern "C" int mli_live_rays(const mli_live_rays_args* a, mli_stream_t s) {
+  if (a->R <= 0 || a->N <= 0 || a->N % 32 != 0 || 256 % a->N != 0 || a->R % (256 / a->N) != 0)
+    return (int)hipErrorInvalidValue;
+  if (!a->weights || !a->flags || !a->tile_list || !a->tile_rank || !a->n_live_tiles) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(live_flags_kernel, dim3((a->R + LR_RAYS - 1) / LR_RAYS), dim3(4 * LR_RAYS), 0, (hipStream_t)s, *a);
+  hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(LR_SCAN), 0, (hipStream_t)s, *a);
+  MLI_LAUNCH_CHECK();
+}

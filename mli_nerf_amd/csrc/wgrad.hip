@@ -47,7 +47,17 @@ struct KArgs {
   int share;                 // SHARE_B layout (see wgrad_kernel): the launch picks that kernel
   float* part;               // deterministic: per-job slabs [n_split][M*K + M], else NULL
   int64_t part_base[MAXJOBS];
+  // live rays (mli_wgrad_args.tile_rank / tile_list; the fragment-image kernel only), else NULL
+  const int* tile_rank; const int* tile_list;
 };
+
+// A wave-uniform int32 through the scalar cache, waited for on the spot (lgkmcnt): a
+// compiler-visible load inside the DMA ring would be waited for with vmcnt(0), draining the ring.
+MLI_FI int sload_i32(const int* p) {
+  int v;
+  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(p) : "memory");
+  return v;
+}
 
 // Rows [t*ROWS, t*ROWS + ROWS) x BK samples from k, 8 x 16 B per row, rows clamped to n_rows.
 template <int ROWS, int LOADS, bool KEEP = false>
@@ -410,9 +420,18 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
   const int split = local % ka.n_split;
   const int tt = local / ka.n_split;
   const int tm = tt / J.tiles_n, tn = tt - tm * J.tiles_n;
-  const int k0 = split * ka.k_split;
-  const int k1 = min(ka.S, k0 + ka.k_split);
+  int k0 = split * ka.k_split;
+  int k1 = min(ka.S, k0 + ka.k_split);
   if (k0 >= k1) return;
+  if (ka.tile_rank != nullptr) {
+    // live rays: the slice of the original samples streams its live tiles, a contiguous range of
+    // the compact images; [k0, k1) are compact sample positions from here on (whole 32-sample
+    // tiles: STG == 32).  A slice without a live tile issues no DMA: nothing to add (atomics),
+    // or its zero slab (deterministic).
+    k0 = ka.tile_rank[k0 >> 5] * 32;
+    k1 = ka.tile_rank[k1 >> 5] * 32;
+    if (k0 >= k1 && ka.part == nullptr) return;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave - wm * WN;
   const int h = lane >> 5, rl = lane & 31;
@@ -553,7 +572,9 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
       consume(st);
     }
   };
-  if constexpr (CAN_RB) {
+  // (n_st == 0: a live-ray slice without a live tile -- no DMA, the zero accumulators go out)
+  if (n_st <= 0) {
+  } else if constexpr (CAN_RB) {
     if (J.rb_dz4 != nullptr) {
       // The same ring for B alone.  Iteration st also issues the rebuild inputs E of stage
       // st + NBUF (before its B DMAs, so that B(st) landed implies E(st + 1) landed: no wait of
@@ -583,7 +604,9 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
           const int kk = min(k0 + s * STG, k1 - STG);
           const uint8_t* p;
           if (wv == 0) {  // lane (c, hh): floats 4 hh .. 4 hh + 3 of sample c's dz4 row
-            const int m = kk + c, r = m / J.rb_N, k = m - r * J.rb_N;
+            // (live rays: the rows of the compact tile's original tile)
+            const int m = (ka.tile_list ? sload_i32(ka.tile_list + (kk >> 5)) * 32 : kk) + c;
+            const int r = m / J.rb_N, k = m - r * J.rb_N;
             p = reinterpret_cast<const uint8_t*>(J.rb_dz4) + ((size_t)k * J.rb_R + r) * 32 + h * 16;
           } else {
             p = J.rb_mask + (size_t)(kk >> 5) * 1024 + lane * 16;
@@ -775,6 +798,9 @@ __global__ __launch_bounds__(256) void dw4_partial_kernel(mli_dw4_args a) {
   for (int g = g0; g < g1; ++g) {
     const int r0 = g * 256 / N, nseg = (g * 256 + 255) / N - r0 + 1;
     for (int sg = 0; sg < nseg; ++sg) {
+      // live rays: a ray without a live tile (pad rays too) adds exact zeros and its q4 item was
+      // not written (or, a pad ray's, is all zero): skipped
+      if (a.tile_rank != nullptr && a.tile_rank[(r0 + sg + 1) * (N / 32)] == a.tile_rank[(r0 + sg) * (N / 32)]) continue;
       const float* d = a.dray + 8 * (r0 + sg);
       const f32x4* q = reinterpret_cast<const f32x4*>(a.q4) + ((size_t)g * segs + sg) * nh * 257;
 #pragma unroll
@@ -893,6 +919,7 @@ int64_t plan(const mli_wgrad_args* a, int cls, bool frag, KArgs& ka) {
   }
   ka.n_jobs = n;
   ka.part = nullptr;
+  ka.tile_rank = ka.tile_list = nullptr;
   if (n == 0) return 0;
   // SHARE: every job is one tile over the same B rows -> the jobs of a k-slice run side by side
   // on one XCD (wgrad_kernel).  Its 32 CUs must hold them all in one round: a 33rd workgroup on
@@ -930,6 +957,12 @@ int launch(const mli_wgrad_args* a, int cls, bool frag, hipStream_t s) {
   }
   int grid = 0;
   for (int i = 0; i < ka.n_jobs; ++i) grid += ((ka.jobs[i].M + BM - 1) / BM) * ka.jobs[i].tiles_n * ka.n_split;
+  if (a->tile_rank != nullptr) {
+    // live rays: the fragment-image kernel's stages of one 32-sample tile only
+    if (!frag || FRAG_TPS != 1 || a->tile_list == nullptr) return (int)hipErrorInvalidValue;
+    ka.tile_rank = a->tile_rank;
+    ka.tile_list = a->tile_list;
+  }
   if (frag) {
     // fragment images: the LDS-DMA ring, FRAG_NBUF stages of FRAG_TPS tiles
     constexpr int LDS = FRAG_NBUF * FRAG_TPS * (BM / 16 + BN / 16) * 1024;
@@ -1024,6 +1057,7 @@ static int dw4_slices(const mli_dw4_args* a) { return std::min(DW4_SLICES, a->R 
 
 extern "C" int mli_dw4(const mli_dw4_args* a, mli_stream_t s) {
   if (!dw4_valid(a) || !a->q4 || !a->dray || !a->workspace) return (int)hipErrorInvalidValue;
+  if (a->tile_rank && 256 % a->N != 0) return (int)hipErrorInvalidValue;
   for (int h = 0; h < a->n_heads; ++h)
     if (!a->dw[h] || !a->db[h]) return (int)hipErrorInvalidValue;
   const int slices = dw4_slices(a);

@@ -162,6 +162,10 @@ class RenderEngine:
         # layer-3 dW jobs rebuild it from dz4, the ReLU mask and W4^T (mli_wgrad_job.rb_*),
         # bit-identical; MLI_DZ3_REBUILD=0: the stored image (A/B runs)
         self.dz3_rebuild = os.environ.get("MLI_DZ3_REBUILD", "1") != "0"
+        # heads(elide=True) (the fused stage-b train step): the heads, their backward and the weight
+        # gradients run only for the rays with a composite weight != 0 (mli_live_rays),
+        # value-identical; MLI_ELIDE_DEAD=0: the dense path (A/B runs)
+        self.elide_dead_rays = os.environ.get("MLI_ELIDE_DEAD", "1") != "0"
         # stage-b training: the output layers' dW from per-tile partials the heads forward forms
         # while X3 is in registers (mli_rgb_fwd PQ mode + mli_dw4) instead of X3 through HBM and
         # the THIN split-K GEMM; needs N % 32 == 0 (a 32-sample tile within one ray)
@@ -359,9 +363,19 @@ class RenderEngine:
         return w
 
     @torch.no_grad()
-    def heads(self, rays, dists, fld, training, s_var=None, progress=0.0):
+    def elides(self, N, training):
+        """heads(elide=True) skips the dead rays for this render: PQ mode (the composite weights
+        are known before the heads run) and whole rays per 256-sample workgroup."""
+        return bool(self.elide_dead_rays and self.pq_mode(N, training) and 256 % N == 0)
+
+    @torch.no_grad()
+    def heads(self, rays, dists, fld, training, s_var=None, progress=0.0, elide=False):
         """Heads forward; stage-b training with ``s_var`` given (and N % 32 == 0) runs the PQ
-        mode: the composite weights first, then the heads with the output-layer partials."""
+        mode: the composite weights first, then the heads with the output-layer partials.
+        ``elide`` (the fused train step; PQ mode and 256 % N == 0, see elides()): only the live
+        rays are processed, in compact order -- the stored images (x0T, xT, masks and the
+        backward's dzT) then hold the tiles hd["tile_list"][:n_live_tiles], not every tile of the
+        batch, so a caller that reads them back by tile index leaves it off."""
         N, R = dists.shape
         S = N * R
         if S % 256:
@@ -391,11 +405,22 @@ class RenderEngine:
         if pq:
             w = self.weights(rays, dists, fld, s_var, progress)
             q4 = self._buf("q4", (S // 256, layout.q4_segs(N), nh, 257, 4))
+        tl = tr = nl = None
+        if pq and elide and self.elides(N, training):
+            # the live rays of this batch, from the weights just computed (device side: the grids
+            # stay S / 256 and the workgroups past the live tiles return at once)
+            tl = self._buf("tile_list", (S // 32,), torch.int32)
+            tr = self._buf("tile_rank", (S // 32 + 1,), torch.int32)
+            nl = self._buf("n_live_tiles", (1,), torch.int32)
+            L.call("mli_live_rays", L.LiveRaysArgs(R, N, L.ptr(w), L.ptr(y),
+                                                   L.ptr(self._buf("live_flags", (R,), torch.int32)),
+                                                   L.ptr(tl), L.ptr(tr), L.ptr(nl)))
         L.call("mli_rgb_fwd", L.RgbFwdArgs(R, N, L.ptr(rays["center"]), L.ptr(rays["ray_unit"]),
                                            L.ptr(rays["pts_light"]), L.ptr(dists), L.ptr(fld["grad"]),
                                            L.ptr(fld["h0"]), L.ptr(self.wfwd), L.ptr(y), L.ptr(feat),
-                                           L.ptr(xT), L.ptr(masks), nh, L.ptr(w), L.ptr(q4)))
-        return dict(y=y, x0T=feat if training else None, xT=xT, masks=masks, feat=feat, q4=q4)
+                                           L.ptr(xT), L.ptr(masks), nh, L.ptr(w), L.ptr(q4), L.ptr(tl), L.ptr(nl)))
+        return dict(y=y, x0T=feat if training else None, xT=xT, masks=masks, feat=feat, q4=q4,
+                    tile_list=tl, tile_rank=tr, n_live_tiles=nl)
 
     @torch.no_grad()
     def composite(self, rays, dists, fld, hd, s_var, progress, training):
@@ -505,14 +530,15 @@ class RenderEngine:
                 return
         raise RuntimeError("render state of an unknown engine lane")
 
-    def render(self, data, s_var, progress, training, u=None, W=512, composite=True):
+    def render(self, data, s_var, progress, training, u=None, W=512, composite=True, elide=False):
         """rays -> sampling -> FIELD -> heads -> composite; ``composite=False`` stops after the
-        heads (comp None: the fused training tail, composite_loss, composites)."""
+        heads (comp None: the fused training tail, composite_loss, composites); ``elide``: as
+        heads()."""
         self._bufs["__gen"] = self._bufs.get("__gen", 0) + 1
         rays = self.rays(data["pose"], data["intr"], data["pose_light"], data["ray_idx"], W)
         dists = self.sample(rays, u)
         fld = self.field(rays, dists, training)
-        hd = self.heads(rays, dists, fld, training, s_var, progress)
+        hd = self.heads(rays, dists, fld, training, s_var, progress, elide=elide)
         if not composite:
             return rays, dists, fld, hd, None
         comp = self.composite(rays, dists, fld, hd, s_var, progress, training)
@@ -593,10 +619,12 @@ class RenderEngine:
         self._wplans[key] = plan
         return plan
 
-    def _wgrad(self, S, jobs, classes):
+    def _wgrad(self, S, jobs, classes, hd=None):
         """mli_wgrad over `classes` (separate launches, timed separately); deterministic mode:
         partial slabs in a workspace sized by mli_wgrad_workspace, else fp32 atomics into the
-        zeroed outputs (the caller zeroes them)."""
+        zeroed outputs (the caller zeroes them).  ``hd``: the heads dict, whose live-ray arrays
+        (heads(elide=True)) go with the call."""
+        tr, tl = (None, None) if hd is None else (hd.get("tile_rank"), hd.get("tile_list"))
         slab = 7 if self.deterministic else self.wgrad_slab_classes
         need = sum(classes) & slab
         ws = None
@@ -607,7 +635,8 @@ class RenderEngine:
         for cls in classes:   # (a mask of several classes: its slab and atomic classes apart)
             for part, det in ((cls & ~slab, 0), (cls & slab, 1)):
                 if part:
-                    L.call("mli_wgrad", L.WgradArgs(S, len(jobs), C.cast(jobs, C.c_void_p), part, det, L.ptr(ws)))
+                    L.call("mli_wgrad", L.WgradArgs(S, len(jobs), C.cast(jobs, C.c_void_p), part, det, L.ptr(ws),
+                                                    L.ptr(tr), L.ptr(tl)))
 
     @torch.no_grad()
     def backward(self, st, d_rgb, d_o_r, d_o_s, d_o_re, flat, sdf_l1, grad_out, dz4=None, on_class=None):
@@ -623,6 +652,9 @@ class RenderEngine:
         pq = hd.get("q4") is not None
         # (the autograd wrapper, dz4 None, keeps the stored dZ3: its callers read dzT afterwards)
         rebuild = self.dz3_rebuild and dz4 is not None
+        if dz4 is None and hd.get("tile_list") is not None:
+            raise RuntimeError("backward: the heads ran with elide=True (the fused train step's mode); the "
+                               "three-call tail needs the dense images")
         if dz4 is None:
             dz4 = self._buf("dz4", (N, R, 8))
             c = lambda t: None if t is None else t.contiguous()  # noqa: E731
@@ -639,7 +671,8 @@ class RenderEngine:
             self._dw_zero = None     # (accumulating from here on, until the assemble zeroes it)
         dzT = self._buf("dzT", (3, 4, S * 256), torch.float16)  # ACC frag images
         L.call("mli_rgb_bwd", L.RgbBwdArgs(R, N, L.ptr(dz4), L.ptr(self.wbwd), L.ptr(hd["masks"]), L.ptr(dzT),
-                                           L.ptr(dz4T), 1 if rebuild else 0))
+                                           L.ptr(dz4T), 1 if rebuild else 0, L.ptr(hd.get("tile_list")),
+                                           L.ptr(hd.get("n_live_tiles"))))
         jobs, ad, (dw4, db4, k4) = self._wgrad_plan(dzT, dz4T, hd, dwbuf, flat, grad_out, S,
                                                     (dz4, R, N) if rebuild else None)
         if self.gate_wgrad:  # Trainer.prefetch(gate="wgrad"): next geometry may start here
@@ -648,9 +681,9 @@ class RenderEngine:
         if on_class is None:   # one assemble launch once every dW class is done
             if pq:
                 self._dw4(R, N, hd, scale, dw4, db4, k4)
-                self._wgrad(S, jobs, (1, 2))  # BIG, WIDE
+                self._wgrad(S, jobs, (1, 2), hd)  # BIG, WIDE
             else:
-                self._wgrad(S, jobs, (1, 2, 4))  # BIG, WIDE, THIN launch classes
+                self._wgrad(S, jobs, (1, 2, 4), hd)  # BIG, WIDE, THIN launch classes
             L.call("mli_grad_assemble", L.AssembleArgs(15, L.ptr(ad), 1.0 / scale, zero_dw))
             self._dw_zero = dwbuf.data_ptr() if zero_dw else None
             return grad_out
@@ -664,9 +697,9 @@ class RenderEngine:
                 if pq:
                     self._dw4(R, N, hd, scale, dw4, db4, k4)
                 else:
-                    self._wgrad(S, jobs, (4,))
+                    self._wgrad(S, jobs, (4,), hd)
             else:
-                self._wgrad(S, jobs, (1,) if cls == "big" else (2,))
+                self._wgrad(S, jobs, (1,) if cls == "big" else (2,), hd)
             n = nh * len(GRAD_CLASS_LAYERS[cls])
             L.call("mli_grad_assemble", L.AssembleArgs(n, L.ptr(ad) + first * sz, 1.0 / scale, zero_dw))
             first += n
@@ -683,7 +716,8 @@ class RenderEngine:
     def _dw4(self, R, N, hd, scale, dw4, db4, k4):
         """PQ mode: the output layers' dW / db from the forward's q4 and the per-ray D."""
         args = L.Dw4Args(R, N, 3, L.ptr(hd["q4"]), L.ptr(self._bufs["dray"]), scale / L.Q4_SCALE,
-                         (C.c_void_p * 3)(*dw4), (C.c_void_p * 3)(*db4), (C.c_int * 3)(*k4), None)
+                         (C.c_void_p * 3)(*dw4), (C.c_void_p * 3)(*db4), (C.c_int * 3)(*k4), None,
+                         L.ptr(hd.get("tile_rank")))
         args.workspace = L.ptr(self._buf("dw4_ws", (L.workspace("mli_dw4", args)[0] // 4,)))
         L.call("mli_dw4", args)
 

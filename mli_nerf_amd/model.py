@@ -255,6 +255,7 @@ class Model(torch.nn.Module):
         self.deterministic = False  # fixed-order gradient reductions (RenderEngine.deterministic)
         self.pq = True              # stage-b output-layer dW from the forward's partials (RenderEngine.pq)
         self.dz3_rebuild = None     # True / False: override RenderEngine.dz3_rebuild (None: its default)
+        self.elide_dead_rays = None  # True / False: override RenderEngine.elide_dead_rays (None: its default)
 
     # -------------------------------------------------------------- parameter plumbing
     def _view(self, name, flat=None):
@@ -382,6 +383,8 @@ class Model(torch.nn.Module):
         eng.pq = self.pq
         if self.dz3_rebuild is not None:
             eng.dz3_rebuild = self.dz3_rebuild
+        if self.elide_dead_rays is not None:
+            eng.elide_dead_rays = self.elide_dead_rays
         eng.set_normal_eps(sdf.normal_eps)
         eng.active_levels = int(sdf.active_levels)
         l0 = sdf.mlp.linears[0]

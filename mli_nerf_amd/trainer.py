@@ -825,12 +825,12 @@ class Trainer:
         fused = self.fused_tail
         if pf is None:
             st = eng.render(data, m.s_var.detach(), m.progress, True, u=m.stratified_uniforms(data, u),
-                            W=m.image_width, **({"composite": False} if fused else {}))
+                            W=m.image_width, **({"composite": False, "elide": True} if fused else {}))
         else:
             lane, rays, dists, fld, done = pf
             torch.cuda.current_stream(m.flat.device).wait_event(done)
             eng.use_lane(lane, geometry_only=True)
-            hd = eng.heads(rays, dists, fld, True, m.s_var.detach(), m.progress)
+            hd = eng.heads(rays, dists, fld, True, m.s_var.detach(), m.progress, elide=fused)
             comp = None if fused else eng.composite(rays, dists, fld, hd, m.s_var.detach(), m.progress, True)
             st = (rays, dists, fld, hd, comp)
         if self.prefetch_gate == "heads":
