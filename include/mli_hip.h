@@ -336,6 +336,15 @@ typedef struct {
    * issues no DMA (deterministic: it writes a zero slab). */
   const int32_t* tile_rank; /* [S/32 + 1] */
   const int32_t* tile_list; /* [S/32] */
+  /* Nonzero tiles, optional (both NULL: every compact tile of the range is streamed; only with the
+   * live-ray arrays above): the lists of mli_live_tiles.  The slice's compact range [c0, c1) maps to
+   * the entries [wtile_rank[c0], wtile_rank[c1]) of wtile_list, and stage i streams the compact
+   * tile wtile_list[i] (a rebuild job: the dz4 rows of tile_list[wtile_list[i]]).  The compact
+   * tiles left out have all-zero composite weights, so their A operand (a dZ image) is all +-0 and
+   * they add +-0 to every sum: the partition and the order of the sums stay as they are.  (With a
+   * non-finite per-ray factor D the dense sum would hold 0 * inf = NaN there; see INTEGRATION.md.) */
+  const int32_t* wtile_rank; /* [S/32 + 1] */
+  const int32_t* wtile_list; /* [wtile_rank[S/32]] */
 } mli_wgrad_args;
 int mli_wgrad(const mli_wgrad_args* a, mli_stream_t s);
 /* bytes[0]: workspace (0 unless deterministic): the largest class in `classes`. */
@@ -388,6 +397,37 @@ struct mli_live_rays_args_s {
 };
 typedef struct mli_live_rays_args_s mli_live_rays_args;
 int mli_live_rays(const mli_live_rays_args* a, mli_stream_t s);
+
+/* mli_live_tiles: the weights pass (mli_composite_fwd with y = NULL; comp.y must be NULL and the
+ * weights it stores are bit-identical to that call's) and every live list from one pass over the
+ * rays.  From the weights a ray's lanes hold in registers it writes flags[r] -- bit j set when
+ * tile j of the ray (samples 32 j .. 32 j + 31) has a weight with a nonzero bit pattern (+-0.0
+ * dead, denormals and NaN live); the ray is live when flags[r] != 0 -- and zeroes the y rows of
+ * the dead rays (of nothing else).  Then a scan over the R flags in ray order (no atomics in the
+ * lists) writes tile_list, tile_rank and n_live_tiles exactly as mli_live_rays does, and beside
+ * them the nonzero tiles in compact order:
+ *   wtile_list [W]        the compact positions p (ascending) whose original tile tile_list[p]
+ *                         has a nonzero weight; W <= L T.  Dead and pad rays have none.  Entries
+ *                         from W on are not written.
+ *   wtile_rank [S/32 + 1] entries of wtile_list below compact position p; wtile_rank[p] = W for
+ *                         every p >= L T.
+ * mli_wgrad streams only these tiles (mli_wgrad_args.wtile_rank / wtile_list).
+ * scan_launch == 0: one launch -- every workgroup draws a ticket (a device-scope fetch-add after
+ * a __threadfence()); the one that draws the last runs the scan and stores 0 back to *ticket,
+ * which the caller zeroes once, at allocation; nobody waits for another workgroup.
+ * scan_launch != 0: the scan is a second launch of one workgroup and ticket is not used.
+ * 256 % N == 0, R % (256 / N) == 0. */
+struct mli_live_tiles_args_s {
+  mli_composite_args comp; /* as mli_composite_fwd, y == NULL; weights [N][R] is written */
+  float* y;                /* [N][R][8] or NULL */
+  int32_t* flags;          /* [R] */
+  int32_t* tile_list; int32_t* tile_rank; int32_t* n_live_tiles;
+  int32_t* wtile_list; int32_t* wtile_rank;
+  int32_t* ticket;         /* one word, 0 between launches (scan_launch == 0) */
+  int scan_launch;
+};
+typedef struct mli_live_tiles_args_s mli_live_tiles_args;
+int mli_live_tiles(const mli_live_tiles_args* a, mli_stream_t s);
 
 /* ---------------------------------------------------------------- stage a (geometry training)
  * Backward of the whole render w.r.t. the geometry: replaces autograd through

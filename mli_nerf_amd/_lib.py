@@ -93,7 +93,7 @@ def frag_job(a, b, M, K, dw, db, ldw, a_kst, b_kst, order=FRAG_ACC, b_order=None
 
 class WgradArgs(C.Structure):
     _fields_ = [("S", I32), ("n_jobs", I32), ("jobs", P), ("classes", I32), ("deterministic", I32),
-                ("workspace", P), ("tile_rank", P), ("tile_list", P)]
+                ("workspace", P), ("tile_rank", P), ("tile_list", P), ("wtile_rank", P), ("wtile_list", P)]
 
 
 class Dw4Args(C.Structure):
@@ -105,6 +105,11 @@ class Dw4Args(C.Structure):
 class LiveRaysArgs(C.Structure):
     _fields_ = [("R", I32), ("N", I32), ("weights", P), ("y", P), ("flags", P), ("tile_list", P),
                 ("tile_rank", P), ("n_live_tiles", P)]
+
+
+class LiveTilesArgs(C.Structure):
+    _fields_ = [("comp", CompositeArgs), ("y", P), ("flags", P), ("tile_list", P), ("tile_rank", P),
+                ("n_live_tiles", P), ("wtile_list", P), ("wtile_rank", P), ("ticket", P), ("scan_launch", I32)]
 
 
 Q4_SCALE = 65536.0  # include/mli_hip.h MLI_Q4_SCALE
@@ -217,6 +222,7 @@ ENTRY_POINTS = {
     "mli_rgb_fwd": RgbFwdArgs, "mli_composite_fwd": CompositeArgs,
     "mli_composite_bwd": CompositeBwdArgs, "mli_rgb_bwd": RgbBwdArgs,
     "mli_wgrad": WgradArgs, "mli_dw4": Dw4Args, "mli_live_rays": LiveRaysArgs,
+    "mli_live_tiles": LiveTilesArgs,
     "mli_pack": PackArgs, "mli_pack_sdf": PackSdfArgs, "mli_grad_assemble": AssembleArgs,
     "mli_adamw": AdamwArgs, "mli_cast_f16": CastArgs, "mli_stage_b_loss": LossArgs,
     "mli_composite_bwd_geo": CompositeBwdGeoArgs, "mli_geo_bwd": GeoBwdArgs, "mli_sdf_bwd": SdfBwdArgs,

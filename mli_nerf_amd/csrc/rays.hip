@@ -908,3 +908,137 @@ extern "C" int mli_live_rays(const mli_live_rays_args* a, mli_stream_t s) {
   hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(LR_SCAN), 0, (hipStream_t)s, *a);
   MLI_LAUNCH_CHECK();
 }
+
+// ---------------------------------------------------------------------- live tiles
+// mli_live_tiles: the weights pass of mli_composite_fwd (y = NULL; composite_ray, the same L, so
+// the same weights bit for bit) with the flag pass of mli_live_rays folded in -- a ray's lanes
+// hold its weights in registers -- and per 32-sample tile instead of per ray: flags[r] bit j =
+// tile j of the ray has a weight with a nonzero bit pattern.  The scan (live_scan_kernel's, plus
+// the nonzero tiles in compact order: wtile_list / wtile_rank, include/mli_hip.h) runs in the
+// workgroup that draws the last ticket, or as a second launch (scan_launch).
+namespace {
+
+constexpr int LT_WAVES = LR_SCAN / 64;  // the pass's workgroups have the scan's thread count
+
+// One workgroup of LR_SCAN threads.  The flags come from other workgroups of the same launch
+// (last-ticket mode): read at agent scope, past this CU's and XCD's caches.
+MLI_FI void live_tiles_scan(const mli_live_tiles_args& a) {
+  __shared__ int sums[2][LR_SCAN];
+  const int t = threadIdx.x;
+  const int R = a.comp.R, N = a.comp.N;
+  const int T = N / 32, G = 256 / N;
+  auto flag_of = [&](int r) MLI_LAMBDA_FI {
+    return (uint32_t)__hip_atomic_load(a.flags + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  // thread t: rays [r0, r1), a contiguous chunk in ray order
+  const int per = (R + LR_SCAN - 1) / LR_SCAN;
+  const int r0 = min(t * per, R), r1 = min(r0 + per, R);
+  int cnt = 0, wcnt = 0;
+  for (int r = r0; r < r1; ++r) {
+    const uint32_t f = flag_of(r);
+    cnt += f != 0;
+    wcnt += __popc(f);
+  }
+  sums[0][t] = cnt;
+  sums[1][t] = wcnt;
+  __syncthreads();
+  // inclusive scans (Hillis-Steele; integer sums: any order gives the same counts)
+  for (int o = 1; o < LR_SCAN; o <<= 1) {
+    const int v = t >= o ? sums[0][t - o] : 0, wv = t >= o ? sums[1][t - o] : 0;
+    __syncthreads();
+    sums[0][t] += v;
+    sums[1][t] += wv;
+    __syncthreads();
+  }
+  const int L = sums[0][LR_SCAN - 1], W = sums[1][LR_SCAN - 1];
+  int before = sums[0][t] - cnt;    // live rays before ray r0
+  int wbefore = sums[1][t] - wcnt;  // nonzero tiles before ray r0 (live rays keep their order)
+  for (int r = r0; r < r1; ++r) {
+    const uint32_t f = flag_of(r);
+    const int live = f != 0;
+    // compact ray position: the live rays first, then the dead ones, each in ascending order
+    const int pos = live ? before : L + (r - before);
+    for (int i = 0; i < T; ++i) {
+      const int below = wbefore + __popc(f & ((1u << i) - 1u));
+      a.tile_list[pos * T + i] = r * T + i;
+      a.tile_rank[r * T + i] = before * T + (live ? i : 0);
+      a.wtile_rank[pos * T + i] = live ? below : W;
+      if ((f >> i) & 1u) a.wtile_list[below] = pos * T + i;
+    }
+    before += live;
+    wbefore += __popc(f);
+  }
+  if (t == 0) {
+    a.tile_rank[R * T] = L * T;
+    a.wtile_rank[R * T] = W;
+    a.n_live_tiles[0] = (L + G - 1) / G * G * T;
+  }
+}
+
+template <int L>
+__global__ __launch_bounds__(LR_SCAN) void live_tiles_kernel(mli_live_tiles_args a) {
+  __shared__ int last;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int sub = lane % L;
+  const int r = (blockIdx.x * LT_WAVES + w) * (64 / L) + lane / L;
+  const int R = a.comp.R, N = a.comp.N;
+  if (r < R) {  // (a ray's lanes take the branch together)
+    float wv[CE], yk[CE][7], acc[12];
+    composite_ray<L>(a.comp, r, sub, wv, yk, acc);
+    // (on the bit pattern: +-0.0 dead, denormals and NaN live, whatever the denormal mode)
+    int nz = 0;
+#pragma unroll
+    for (int e = 0; e < CE; ++e)
+      if (CE * sub + e < N) nz |= (__builtin_bit_cast(uint32_t, wv[e]) & 0x7fffffffu) != 0;
+    // a tile is the samples of 32 / CE consecutive lanes of the ray
+    const uint64_t seg = __ballot(nz) >> (lane / L * L);
+    uint32_t f = 0;
+#pragma unroll
+    for (int j = 0; j < L * CE / 32; ++j)
+      if (j * 32 < N && ((seg >> (j * (32 / CE))) & ((1u << (32 / CE)) - 1u)) != 0) f |= 1u << j;
+    if (sub == 0) a.flags[r] = (int)f;
+    if (f == 0 && a.y != nullptr) {
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int e = 0; e < CE; ++e) {
+        const int k = CE * sub + e;
+        if (k < N) {
+          f32x4* row = reinterpret_cast<f32x4*>(a.y + ((size_t)k * R + r) * 8);
+          row[0] = z;
+          row[1] = z;
+        }
+      }
+    }
+  }
+  if (a.scan_launch) return;
+  // the last workgroup to finish scans: every thread's flag stores are released before the
+  // workgroup draws its ticket; nobody waits for another workgroup
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) last = atomicAdd(a.ticket, 1) == (int)gridDim.x - 1;
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  live_tiles_scan(a);
+  if (threadIdx.x == 0) atomicExch(a.ticket, 0);  // for the next launch
+}
+
+__global__ __launch_bounds__(LR_SCAN) void live_tiles_scan_kernel(mli_live_tiles_args a) { live_tiles_scan(a); }
+
+}  // namespace
+
+extern "C" int mli_live_tiles(const mli_live_tiles_args* a, mli_stream_t s) {
+  const int R = a->comp.R, N = a->comp.N;
+  if (R <= 0 || N <= 0 || N % 32 != 0 || 256 % N != 0 || R % (256 / N) != 0) return (int)hipErrorInvalidValue;
+  if (a->comp.y != nullptr || !a->comp.weights || !a->flags || !a->tile_list || !a->tile_rank || !a->n_live_tiles ||
+      !a->wtile_list || !a->wtile_rank || (!a->scan_launch && !a->ticket))
+    return (int)hipErrorInvalidValue;
+  if (N <= 32 * CE) {  // two rays per wave, as mli_composite_fwd
+    const int rpb = 2 * LT_WAVES;
+    hipLaunchKernelGGL(live_tiles_kernel<32>, dim3((R + rpb - 1) / rpb), dim3(LR_SCAN), 0, (hipStream_t)s, *a);
+  } else {
+    hipLaunchKernelGGL(live_tiles_kernel<64>, dim3((R + LT_WAVES - 1) / LT_WAVES), dim3(LR_SCAN), 0, (hipStream_t)s, *a);
+  }
+  if (a->scan_launch) hipLaunchKernelGGL(live_tiles_scan_kernel, dim3(1), dim3(LR_SCAN), 0, (hipStream_t)s, *a);
+  MLI_LAUNCH_CHECK();
+}

@@ -49,6 +49,8 @@ struct KArgs {
   int64_t part_base[MAXJOBS];
   // live rays (mli_wgrad_args.tile_rank / tile_list; the fragment-image kernel only), else NULL
   const int* tile_rank; const int* tile_list;
+  // nonzero tiles (mli_wgrad_args.wtile_rank / wtile_list; with the live rays only), else NULL
+  const int* wtile_rank; const int* wtile_list;
 };
 
 // A wave-uniform int32 through the scalar cache, waited for on the spot (lgkmcnt): a
@@ -57,6 +59,17 @@ MLI_FI int sload_i32(const int* p) {
   int v;
   asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(p) : "memory");
   return v;
+}
+
+// A wave-uniform int32 into an SGPR whatever register class the compiler computed it in (a
+// uniform select may come out of the VALU, and an "s" operand is not legalised).  The compiler
+// does not see into the statement, so the wait states it would put around the instruction are
+// inside: one after the VALU write of the source VGPR (without it the lane read returns the
+// register's old contents -- an index from nowhere), two before a VALU may read the SGPR.
+MLI_FI int to_sgpr(int v) {
+  int r;
+  asm("s_nop 0\n\tv_readfirstlane_b32 %0, %1\n\ts_nop 1" : "=s"(r) : "v"(v));
+  return r;
 }
 
 // Rows [t*ROWS, t*ROWS + ROWS) x BK samples from k, 8 x 16 B per row, rows clamped to n_rows.
@@ -420,17 +433,28 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
   const int split = local % ka.n_split;
   const int tt = local / ka.n_split;
   const int tm = tt / J.tiles_n, tn = tt - tm * J.tiles_n;
-  int k0 = split * ka.k_split;
-  int k1 = min(ka.S, k0 + ka.k_split);
+  const int k0 = split * ka.k_split;
+  const int k1 = min(ka.S, k0 + ka.k_split);
   if (k0 >= k1) return;
+  // The slice's stages: stage s streams tile t0 + s * TPS of the images, or -- wl set -- the
+  // compact tile wl[s].
+  int t0 = k0 >> 5, n_st = (k1 - k0) / STG;
+  const int* wl = nullptr;
   if (ka.tile_rank != nullptr) {
     // live rays: the slice of the original samples streams its live tiles, a contiguous range of
-    // the compact images; [k0, k1) are compact sample positions from here on (whole 32-sample
-    // tiles: STG == 32).  A slice without a live tile issues no DMA: nothing to add (atomics),
-    // or its zero slab (deterministic).
-    k0 = ka.tile_rank[k0 >> 5] * 32;
-    k1 = ka.tile_rank[k1 >> 5] * 32;
-    if (k0 >= k1 && ka.part == nullptr) return;
+    // the compact images (whole 32-sample tiles: STG == 32).  A slice without a live tile issues
+    // no DMA: nothing to add (atomics), or its zero slab (deterministic).
+    t0 = __builtin_amdgcn_readfirstlane(ka.tile_rank[k0 >> 5]);
+    n_st = __builtin_amdgcn_readfirstlane(ka.tile_rank[k1 >> 5]) - t0;
+    if (ka.wtile_rank != nullptr) {
+      // nonzero tiles: of that range only the tiles with a nonzero composite weight, a contiguous
+      // range of wtile_list; a tile left out simply is not a stage
+      // (the counts made scalar: the list entries are scalar loads)
+      const int i0 = __builtin_amdgcn_readfirstlane(ka.wtile_rank[t0]);
+      n_st = __builtin_amdgcn_readfirstlane(ka.wtile_rank[t0 + n_st]) - i0;
+      wl = ka.wtile_list + i0;
+    }
+    if (n_st <= 0 && ka.part == nullptr) return;
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave - wm * WN;
@@ -467,12 +491,18 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
   // lane (c, hh) of an even k-step's piece: 16 B at (32 hh + (c ^ 4 hh)) * 16; odd: c ^ 8 as well
   const uint32_t voff = (32 * (lane >> 5) + ((lane & 31) ^ ((lane >> 5) << 2))) * 16;
   // RB (a rebuild job, below): only the B pieces; the A block is written by the waves
+  // the first tile of stage s; past the end: the slice's last stage again (a dummy refetch, never
+  // consumed).  The list entry is a scalar load waited for on the spot (sload_i32).
+  auto tile_of = [&](int s) MLI_LAMBDA_FI {
+    const int sc = min(s, n_st - 1);
+    return wl != nullptr ? sload_i32(wl + to_sgpr(sc)) : t0 + sc * TPS;
+  };
   auto issue = [&](auto RBc, int s, int buf) MLI_LAMBDA_FI {
     constexpr int U0 = decltype(RBc)::value ? A_PPW : 0;
-    const int kk = min(k0 + s * STG, k1 - STG);  // past the end: a dummy refetch, never consumed
+    const int tile = tile_of(s);
 #pragma unroll
     for (int u = U0; u < PPW; ++u) {
-      const uint8_t* sp = sbase[u] + (size_t)(kk >> 5) * tstride[u];
+      const uint8_t* sp = sbase[u] + (size_t)tile * tstride[u];
       glds16(sp + (voff ^ (uint32_t)odd[u]), lds + buf * STAGE + piece_of(u) * 1024);
     }
   };
@@ -507,7 +537,6 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
   for (int i = 0; i < TM; ++i) bsum[i] = 0.f;
   const half2 ones = {(f16)1.f, (f16)1.f};
 
-  const int n_st = (k1 - k0) / STG;
   // the MFMAs of stage st (its operand blocks are in LDS buffer st % NBUF)
   auto consume = [&](int st) MLI_LAMBDA_FI {
     const uint32_t so = (st % NBUF) * STAGE;
@@ -601,15 +630,15 @@ __global__ __launch_bounds__(512) void wgrad_frag_kernel(KArgs ka) {
       tie(bias);
       auto issue_e = [&](int s) MLI_LAMBDA_FI {
         if (wv < 2) {
-          const int kk = min(k0 + s * STG, k1 - STG);
+          const int tile = tile_of(s);
           const uint8_t* p;
           if (wv == 0) {  // lane (c, hh): floats 4 hh .. 4 hh + 3 of sample c's dz4 row
             // (live rays: the rows of the compact tile's original tile)
-            const int m = (ka.tile_list ? sload_i32(ka.tile_list + (kk >> 5)) * 32 : kk) + c;
+            const int m = (ka.tile_list ? sload_i32(ka.tile_list + tile) : tile) * 32 + c;
             const int r = m / J.rb_N, k = m - r * J.rb_N;
             p = reinterpret_cast<const uint8_t*>(J.rb_dz4) + ((size_t)k * J.rb_R + r) * 32 + h * 16;
           } else {
-            p = J.rb_mask + (size_t)(kk >> 5) * 1024 + lane * 16;
+            p = J.rb_mask + (size_t)tile * 1024 + lane * 16;
           }
           glds16(p, lds + E_OFF + (s % NBUF) * E_SLOT + wv * 1024);
         }
@@ -919,7 +948,7 @@ int64_t plan(const mli_wgrad_args* a, int cls, bool frag, KArgs& ka) {
   }
   ka.n_jobs = n;
   ka.part = nullptr;
-  ka.tile_rank = ka.tile_list = nullptr;
+  ka.tile_rank = ka.tile_list = ka.wtile_rank = ka.wtile_list = nullptr;
   if (n == 0) return 0;
   // SHARE: every job is one tile over the same B rows -> the jobs of a k-slice run side by side
   // on one XCD (wgrad_kernel).  Its 32 CUs must hold them all in one round: a 33rd workgroup on
@@ -962,6 +991,12 @@ int launch(const mli_wgrad_args* a, int cls, bool frag, hipStream_t s) {
     if (!frag || FRAG_TPS != 1 || a->tile_list == nullptr) return (int)hipErrorInvalidValue;
     ka.tile_rank = a->tile_rank;
     ka.tile_list = a->tile_list;
+  }
+  if (a->wtile_rank != nullptr || a->wtile_list != nullptr) {
+    // nonzero tiles: both lists, on top of the live rays
+    if (a->tile_rank == nullptr || a->wtile_rank == nullptr || a->wtile_list == nullptr) return (int)hipErrorInvalidValue;
+    ka.wtile_rank = a->wtile_rank;
+    ka.wtile_list = a->wtile_list;
   }
   if (frag) {
     // fragment images: the LDS-DMA ring, FRAG_NBUF stages of FRAG_TPS tiles

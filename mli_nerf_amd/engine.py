@@ -166,6 +166,15 @@ class RenderEngine:
         # gradients run only for the rays with a composite weight != 0 (mli_live_rays),
         # value-identical; MLI_ELIDE_DEAD=0: the dense path (A/B runs)
         self.elide_dead_rays = os.environ.get("MLI_ELIDE_DEAD", "1") != "0"
+        # with the elision: the weights and every live list come from one pass over the rays
+        # (mli_live_tiles) instead of mli_composite_fwd + mli_live_rays; 1: the scan is a second
+        # launch, 2: the last workgroup of the pass scans (one launch), 0: the three launches
+        # (A/B runs; DESIGN.md §9.12 has the measurements behind the default)
+        self.live_tiles_pass = int(os.environ.get("MLI_LIVE_TILES_PASS", "1"))
+        # ... and the dW kernels stream only the tiles with a nonzero composite weight (a tile of
+        # a live ray whose weights are all zero adds +-0 to every sum); MLI_SKIP_ZERO_TILES=0:
+        # every tile of the live rays (A/B runs).  Needs the lists of mli_live_tiles.
+        self.skip_zero_tiles = os.environ.get("MLI_SKIP_ZERO_TILES", "1") != "0"
         # stage-b training: the output layers' dW from per-tile partials the heads forward forms
         # while X3 is in registers (mli_rgb_fwd PQ mode + mli_dw4) instead of X3 through HBM and
         # the THIN split-K GEMM; needs N % 32 == 0 (a 32-sample tile within one ray)
@@ -402,25 +411,43 @@ class RenderEngine:
         if training:
             xT = self._buf("xT", (nh, 3 if pq else 4, S * 256), torch.float16)  # ACC frag images
             masks = self._buf("masks", (nh, 4, S // 32, 64, 4), torch.int32)
-        if pq:
-            w = self.weights(rays, dists, fld, s_var, progress)
-            q4 = self._buf("q4", (S // 256, layout.q4_segs(N), nh, 257, 4))
-        tl = tr = nl = None
-        if pq and elide and self.elides(N, training):
-            # the live rays of this batch, from the weights just computed (device side: the grids
-            # stay S / 256 and the workgroups past the live tiles return at once)
+        tl = tr = nl = wl = wr = None
+        elide = bool(pq and elide and self.elides(N, training))
+        if elide:
+            # the live rays of this batch, from the weights (device side: the grids stay S / 256
+            # and the workgroups past the live tiles return at once)
             tl = self._buf("tile_list", (S // 32,), torch.int32)
             tr = self._buf("tile_rank", (S // 32 + 1,), torch.int32)
             nl = self._buf("n_live_tiles", (1,), torch.int32)
-            L.call("mli_live_rays", L.LiveRaysArgs(R, N, L.ptr(w), L.ptr(y),
-                                                   L.ptr(self._buf("live_flags", (R,), torch.int32)),
-                                                   L.ptr(tl), L.ptr(tr), L.ptr(nl)))
+            flags = self._buf("live_flags", (R,), torch.int32)
+        if elide and self.live_tiles_pass:
+            # the weights, the live rays and the nonzero tiles in one pass
+            w = self._buf("weights", (N, R))
+            out = dict(weights=w, rgb=None, o_r=None, o_s=None, o_re=None)
+            wl = self._buf("wtile_list", (S // 32,), torch.int32)
+            wr = self._buf("wtile_rank", (S // 32 + 1,), torch.int32)
+            ticket = self._bufs.get("live_ticket")
+            if ticket is None:   # zeroed once: the pass leaves it zero
+                ticket = self._bufs["live_ticket"] = torch.zeros(1, dtype=torch.int32, device=self.device)
+            L.call("mli_live_tiles", L.LiveTilesArgs(
+                self._composite_args(rays, dists, fld, dict(y=None), s_var, progress, out), L.ptr(y), L.ptr(flags),
+                L.ptr(tl), L.ptr(tr), L.ptr(nl), L.ptr(wl), L.ptr(wr), L.ptr(ticket),
+                0 if self.live_tiles_pass == 2 else 1))
+            if not self.skip_zero_tiles:
+                wl = wr = None
+        elif pq:
+            w = self.weights(rays, dists, fld, s_var, progress)
+            if elide:
+                L.call("mli_live_rays", L.LiveRaysArgs(R, N, L.ptr(w), L.ptr(y), L.ptr(flags),
+                                                       L.ptr(tl), L.ptr(tr), L.ptr(nl)))
+        if pq:
+            q4 = self._buf("q4", (S // 256, layout.q4_segs(N), nh, 257, 4))
         L.call("mli_rgb_fwd", L.RgbFwdArgs(R, N, L.ptr(rays["center"]), L.ptr(rays["ray_unit"]),
                                            L.ptr(rays["pts_light"]), L.ptr(dists), L.ptr(fld["grad"]),
                                            L.ptr(fld["h0"]), L.ptr(self.wfwd), L.ptr(y), L.ptr(feat),
                                            L.ptr(xT), L.ptr(masks), nh, L.ptr(w), L.ptr(q4), L.ptr(tl), L.ptr(nl)))
         return dict(y=y, x0T=feat if training else None, xT=xT, masks=masks, feat=feat, q4=q4,
-                    tile_list=tl, tile_rank=tr, n_live_tiles=nl)
+                    tile_list=tl, tile_rank=tr, n_live_tiles=nl, wtile_list=wl, wtile_rank=wr)
 
     @torch.no_grad()
     def composite(self, rays, dists, fld, hd, s_var, progress, training):
@@ -624,7 +651,8 @@ class RenderEngine:
         partial slabs in a workspace sized by mli_wgrad_workspace, else fp32 atomics into the
         zeroed outputs (the caller zeroes them).  ``hd``: the heads dict, whose live-ray arrays
         (heads(elide=True)) go with the call."""
-        tr, tl = (None, None) if hd is None else (hd.get("tile_rank"), hd.get("tile_list"))
+        tr, tl, wr, wl = (None,) * 4 if hd is None else [hd.get(k) for k in ("tile_rank", "tile_list", "wtile_rank",
+                                                                             "wtile_list")]
         slab = 7 if self.deterministic else self.wgrad_slab_classes
         need = sum(classes) & slab
         ws = None
@@ -636,7 +664,7 @@ class RenderEngine:
             for part, det in ((cls & ~slab, 0), (cls & slab, 1)):
                 if part:
                     L.call("mli_wgrad", L.WgradArgs(S, len(jobs), C.cast(jobs, C.c_void_p), part, det, L.ptr(ws),
-                                                    L.ptr(tr), L.ptr(tl)))
+                                                    L.ptr(tr), L.ptr(tl), L.ptr(wr), L.ptr(wl)))
 
     @torch.no_grad()
     def backward(self, st, d_rgb, d_o_r, d_o_s, d_o_re, flat, sdf_l1, grad_out, dz4=None, on_class=None):

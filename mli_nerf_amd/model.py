@@ -256,6 +256,7 @@ class Model(torch.nn.Module):
         self.pq = True              # stage-b output-layer dW from the forward's partials (RenderEngine.pq)
         self.dz3_rebuild = None     # True / False: override RenderEngine.dz3_rebuild (None: its default)
         self.elide_dead_rays = None  # True / False: override RenderEngine.elide_dead_rays (None: its default)
+        self.skip_zero_tiles = None  # True / False: override RenderEngine.skip_zero_tiles (None: its default)
 
     # -------------------------------------------------------------- parameter plumbing
     def _view(self, name, flat=None):
@@ -385,6 +386,8 @@ class Model(torch.nn.Module):
             eng.dz3_rebuild = self.dz3_rebuild
         if self.elide_dead_rays is not None:
             eng.elide_dead_rays = self.elide_dead_rays
+        if self.skip_zero_tiles is not None:
+            eng.skip_zero_tiles = self.skip_zero_tiles
         eng.set_normal_eps(sdf.normal_eps)
         eng.active_levels = int(sdf.active_levels)
         l0 = sdf.mlp.linears[0]
