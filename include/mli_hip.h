@@ -138,10 +138,47 @@ typedef struct {
                              as MFMA B-fragment images [S/32][5][8][64][8] fp16 (S*640 halves) */
   int active_levels;      /* coarse-to-fine mask (modules.py:91-93,110-113): levels >= this
                              encode to 0 (stage b / c2f off: MLI_LEVELS)                     */
+  /* Inside rays, optional (both NULL: dense; FIELD mode only, n_per_ray % 32 == 0): the lists of
+   * mli_inside_list.  The grids and the tile chunks stay those of the dense call, over compact
+   * tile indices: with T = n_per_ray / 32, compact tile ci is the original tile
+   * inside_list[ci / T] * T + ci % T, and a workgroup or wave with ci >= *n_inside * T returns
+   * before it gathers anything.  Every buffer is addressed by the original tile / slot, so the
+   * sdf / grad / hess rows and the h0 / enc tiles of the rays outside the bounds are NOT written
+   * (mli_inside_list writes those rows; nobody may read those tiles). */
+  const int32_t* inside_list;
+  const int32_t* n_inside;
 } mli_sdf_args;
 int mli_sdf(const mli_sdf_args* a, mli_stream_t s);
 /* bytes[0]: enc (FIELD mode; 0 in SDF mode). */
 int mli_sdf_workspace(const mli_sdf_args* a, int64_t* bytes);
+
+/* mli_inside_list: the rays a FIELD pass has to evaluate, from the outside flags of mli_rays.  A
+ * ray that misses the bounds has its sdf overwritten with outside_val (NeuralLumen/model.py:343),
+ * which saturates both NeuS sigmoids: its composite weights are exactly 0, its gradients and
+ * hessians are masked out of the eikonal and curvature terms, and its h0 tiles are never live
+ * (mli_live_rays).  One launch, no atomics; it writes
+ *   inside_list [R]      the rays with outside == 0 ascending, then the others ascending
+ *   n_inside    [1]      how many of the first kind, plus min(n_pad, rays of the second kind)
+ * and the rows FIELD would leave for the outside rays, for every sample k < N, [N][R] layout:
+ *   sdf = outside_val, grad = 0, hess = 0 (hess may be NULL); the rows of the other rays are not
+ * touched (sdf / grad NULL: the lists only).
+ * n_pad: the heads process up to 256 / N - 1 dead rays as pads of their last workgroup, the first
+ * dead rays in ray order (mli_live_rays) -- if such a ray is outside the bounds it is among the
+ * first 256 / N - 1 outside rays.  Counting those into n_inside makes the FIELD pass evaluate them
+ * as the dense pass does (it runs after this call and overwrites their constant rows). */
+struct mli_inside_list_args_s {
+  int R, N;
+  int n_pad;              /* >= 0 */
+  const uint8_t* outside; /* [R] */
+  int32_t* inside_list;   /* [R] */
+  int32_t* n_inside;      /* [1] */
+  float outside_val;
+  float* sdf;             /* [N][R] or NULL */
+  float* grad;            /* [N][R][3] or NULL */
+  float* hess;            /* [N][R][3] or NULL */
+};
+typedef struct mli_inside_list_args_s mli_inside_list_args;
+int mli_inside_list(const mli_inside_list_args* a, mli_stream_t s);
 
 /* ---------------------------------------------------------------- sampling
  * Replaces nerf_util.sample_dists (nerf_util.py:20-38), sample_dists_hierarchical

@@ -35,7 +35,12 @@ class SdfArgs(C.Structure):
                 ("dists", P), ("outside", P), ("table", P), ("levels", GridLevels), ("wsdf", P),
                 ("eps", F32), ("grad_den", F32), ("hess_den", F32), ("outside_val", F32),
                 ("with_hessian", I32), ("sdf", P), ("grad", P), ("hess", P), ("h0", P),
-                ("enc", P), ("active_levels", I32)]
+                ("enc", P), ("active_levels", I32), ("inside_list", P), ("n_inside", P)]
+
+
+class InsideListArgs(C.Structure):
+    _fields_ = [("R", I32), ("N", I32), ("n_pad", I32), ("outside", P), ("inside_list", P), ("n_inside", P),
+                ("outside_val", F32), ("sdf", P), ("grad", P), ("hess", P)]
 
 
 class SampleCoarseArgs(C.Structure):
@@ -222,7 +227,7 @@ ENTRY_POINTS = {
     "mli_rgb_fwd": RgbFwdArgs, "mli_composite_fwd": CompositeArgs,
     "mli_composite_bwd": CompositeBwdArgs, "mli_rgb_bwd": RgbBwdArgs,
     "mli_wgrad": WgradArgs, "mli_dw4": Dw4Args, "mli_live_rays": LiveRaysArgs,
-    "mli_live_tiles": LiveTilesArgs,
+    "mli_live_tiles": LiveTilesArgs, "mli_inside_list": InsideListArgs,
     "mli_pack": PackArgs, "mli_pack_sdf": PackSdfArgs, "mli_grad_assemble": AssembleArgs,
     "mli_adamw": AdamwArgs, "mli_cast_f16": CastArgs, "mli_stage_b_loss": LossArgs,
     "mli_composite_bwd_geo": CompositeBwdGeoArgs, "mli_geo_bwd": GeoBwdArgs, "mli_sdf_bwd": SdfBwdArgs,

@@ -909,6 +909,68 @@ extern "C" int mli_live_rays(const mli_live_rays_args* a, mli_stream_t s) {
   MLI_LAUNCH_CHECK();
 }
 
+// ---------------------------------------------------------------------- inside rays
+// mli_inside_list: which rays the FIELD pass must evaluate (include/mli_hip.h).  The first
+// fill_blocks workgroups write the rows FIELD would leave for the rays outside the bounds, one
+// thread per slot k R + r (coalesced over r); the last workgroup scans the R flags in ray order
+// (live_scan_kernel's scan) and writes the list.  The two parts share no data.
+namespace {
+
+__global__ __launch_bounds__(LR_SCAN) void inside_list_kernel(mli_inside_list_args a, int fill_blocks) {
+  __shared__ int sums[LR_SCAN];
+  const int t = threadIdx.x;
+  if ((int)blockIdx.x < fill_blocks) {
+    const size_t i = (size_t)blockIdx.x * LR_SCAN + t;
+    if (i >= (size_t)a.R * a.N) return;
+    if (!a.outside[i % a.R]) return;
+    a.sdf[i] = a.outside_val;
+    a.grad[3 * i] = 0.0f;
+    a.grad[3 * i + 1] = 0.0f;
+    a.grad[3 * i + 2] = 0.0f;
+    if (a.hess != nullptr) {
+      a.hess[3 * i] = 0.0f;
+      a.hess[3 * i + 1] = 0.0f;
+      a.hess[3 * i + 2] = 0.0f;
+    }
+    return;
+  }
+  // thread t: rays [r0, r1), a contiguous chunk in ray order
+  const int per = (a.R + LR_SCAN - 1) / LR_SCAN;
+  const int r0 = min(t * per, a.R), r1 = min(r0 + per, a.R);
+  int cnt = 0;
+  for (int r = r0; r < r1; ++r) cnt += a.outside[r] == 0;
+  sums[t] = cnt;
+  __syncthreads();
+  // inclusive scan (Hillis-Steele; integer sums: any order gives the same counts)
+  for (int o = 1; o < LR_SCAN; o <<= 1) {
+    const int v = t >= o ? sums[t - o] : 0;
+    __syncthreads();
+    sums[t] += v;
+    __syncthreads();
+  }
+  const int n_in = sums[LR_SCAN - 1];
+  int before = sums[t] - cnt;  // inside rays before ray r0
+  for (int r = r0; r < r1; ++r) {
+    const int in = a.outside[r] == 0;
+    a.inside_list[in ? before : n_in + (r - before)] = r;
+    before += in;
+  }
+  if (t == 0) a.n_inside[0] = min(n_in + a.n_pad, a.R);  // the first n_pad outside rays follow the inside ones
+}
+
+}  // namespace
+
+extern "C" int mli_inside_list(const mli_inside_list_args* a, mli_stream_t s) {
+  if (a->R <= 0 || a->N <= 0 || a->n_pad < 0 || !a->outside || !a->inside_list || !a->n_inside)
+    return (int)hipErrorInvalidValue;
+  if ((a->sdf == nullptr) != (a->grad == nullptr) || (a->hess != nullptr && a->sdf == nullptr))
+    return (int)hipErrorInvalidValue;
+  const int64_t S = (int64_t)a->R * a->N;
+  const int fill_blocks = a->sdf ? (int)((S + LR_SCAN - 1) / LR_SCAN) : 0;
+  hipLaunchKernelGGL(inside_list_kernel, dim3(fill_blocks + 1), dim3(LR_SCAN), 0, (hipStream_t)s, *a, fill_blocks);
+  MLI_LAUNCH_CHECK();
+}
+
 // ---------------------------------------------------------------------- live tiles
 // mli_live_tiles: the weights pass of mli_composite_fwd (y = NULL; composite_ray, the same L, so
 // the same weights bit for bit) with the flag pass of mli_live_rays folded in -- a ray's lanes

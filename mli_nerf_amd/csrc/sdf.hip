@@ -333,13 +333,26 @@ MLI_FI void field_points(const mli_sdf_args& a, int slot, int r, float (&q)[TAPS
   }
 }
 
+// Inside-ray list (mli_sdf_args.inside_list): the original tile of compact tile ci, or -1 past
+// the inside rays' tiles.  ci is wave-uniform; the list entry is an ordinary load made scalar.
+MLI_FI int list_tile(const mli_sdf_args& a, int ci) {
+  const int T = a.n_per_ray >> 5;
+  if (ci >= *a.n_inside * T) return -1;
+  const int rc = ci / T;
+  return __builtin_amdgcn_readfirstlane(a.inside_list[rc]) * T + (ci - rc * T);
+}
+
 __global__ __launch_bounds__(256) void encode5_kernel(mli_sdf_args a, int tile0, int tile1) {
   __shared__ TapJob job_lists[4][4 * 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31;
   const int n_total = a.R * a.n_per_ray;
-  const int tile = tile0 + blockIdx.x * 4 + wave;
+  int tile = tile0 + blockIdx.x * 4 + wave;
   if (tile >= tile1) return;
+  if (a.inside_list != nullptr) {
+    tile = list_tile(a, __builtin_amdgcn_readfirstlane(tile));
+    if (tile < 0) return;
+  }
   const int m = min(tile * 32 + c, n_total - 1);
   const int r = m / a.n_per_ray, k = m - r * a.n_per_ray;
   float q[TAPS][3];
@@ -381,11 +394,19 @@ __global__ __launch_bounds__(256) void encode5_kernel(mli_sdf_args a, int tile0,
 template <int MLP_WAVES>
 __global__ __launch_bounds__(MLP_WAVES * 64) void field_mlp_kernel(mli_sdf_args a, int tile0, int tile1) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  const bool listed = a.inside_list != nullptr;
+  if (listed) {
+    // the chunk ends with the inside rays' tiles; a workgroup past them returns before the
+    // weight load and its barrier
+    tile1 = min(tile1, *a.n_inside * (a.n_per_ray >> 5));
+    if (tile0 + (int)blockIdx.x * MLP_WAVES >= tile1) return;
+  }
   load_weights(lds, a.wsdf);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
   const int n_total = a.R * a.n_per_ray;
-  for (int tile = tile0 + blockIdx.x * MLP_WAVES + wave; tile < tile1; tile += gridDim.x * MLP_WAVES) {
+  for (int ci = tile0 + blockIdx.x * MLP_WAVES + wave; ci < tile1; ci += gridDim.x * MLP_WAVES) {
+    const int tile = listed ? list_tile(a, __builtin_amdgcn_readfirstlane(ci)) : ci;
     const uint8_t* lds_t = lds + opaque_v(0);  // keep LDS fragments from being hoisted (registers)
     const int m = tile * 32 + c;
     const bool valid = m < n_total;
@@ -1287,6 +1308,7 @@ extern "C" int mli_sdf(const mli_sdf_args* a, mli_stream_t s) {
   const int tiles = (n_total + 31) / 32;
   if (tiles < 1) return 0;
   if (a->mode == MLI_SDF_MODE_SDF) {
+    if (a->inside_list != nullptr || a->n_inside != nullptr) return (int)hipErrorInvalidValue;  // FIELD only
     int blocks = (tiles + SDF_WAVES - 1) / SDF_WAVES;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sdf_kernel, dim3(blocks), dim3(256), LDS_SDF, (hipStream_t)s, *a);
@@ -1294,13 +1316,21 @@ extern "C" int mli_sdf(const mli_sdf_args* a, mli_stream_t s) {
   }
   if (a->h0 == nullptr || a->grad == nullptr) return (int)hipErrorInvalidValue;
   if (a->enc == nullptr) return (int)hipErrorInvalidValue;
+  // the inside-ray list: both arrays or neither, and whole 32-sample tiles per ray
+  if ((a->inside_list == nullptr) != (a->n_inside == nullptr)) return (int)hipErrorInvalidValue;
+  if (a->inside_list != nullptr && a->n_per_ray % 32 != 0) return (int)hipErrorInvalidValue;
   // FIELD: phase A (encodings of the 5 points) then phase B (layer 0 + softplus + sdf head),
   // in chunks of tiles (a chunk's encodings: tiles x 40 KiB).  Measured at 4096 x 128 samples
   // with the geometry prefetched beside the heads: 1024 / 2048 / 4096 / 8192 /
   // 16384 tiles per chunk give FIELD 1.55 / 1.01 / 0.88 / 0.81 / 0.77 ms and steps of 5.49 /
   // 4.90 / 4.60 / 4.53 / 4.66 ms: each chunk pays a launch tail, and one chunk of 640 MiB
   // crowds the heads; 8192 (320 MiB, half of it re-read from the Infinity Cache) is kept.
-  constexpr int CHUNK_TILES = 8192;
+  // With the inside-ray list the chunks count compact tiles, so the tiles of the rays outside
+  // the bounds leave the last chunks empty (MLI_LIST_CHUNK_TILES: DESIGN 9.13 has the measurement).
+#ifndef MLI_LIST_CHUNK_TILES
+#define MLI_LIST_CHUNK_TILES 8192
+#endif
+  const int CHUNK_TILES = a->inside_list != nullptr ? MLI_LIST_CHUNK_TILES : 8192;
   for (int t0 = 0; t0 < tiles; t0 += CHUNK_TILES) {
     const int t1 = t0 + CHUNK_TILES < tiles ? t0 + CHUNK_TILES : tiles;
     hipLaunchKernelGGL(encode5_kernel, dim3((t1 - t0 + 3) / 4), dim3(256), 0, (hipStream_t)s, *a, t0, t1);

@@ -57,7 +57,7 @@ def _grid_levels(cfg):
 # the only ones a training prefetch lane needs of its own (RenderEngine.use_lane(geometry_only)).
 GEOMETRY_BUFS = frozenset(["center", "ray_unit", "ray_norm", "pts_light", "near", "far", "outside",
                            "d_coarse", "s_coarse", "d_m0", "d_m1", "s_m0", "s_m1", "d_f0", "d_f1", "s_f0",
-                           "s_f1", "dists", "sdf", "grad", "hess", "h0", "enc5"])
+                           "s_f1", "dists", "sdf", "grad", "hess", "h0", "enc5", "inside_list", "n_inside"])
 
 
 class _GeometryLane(dict):
@@ -175,6 +175,11 @@ class RenderEngine:
         # a live ray whose weights are all zero adds +-0 to every sum); MLI_SKIP_ZERO_TILES=0:
         # every tile of the live rays (A/B runs).  Needs the lists of mli_live_tiles.
         self.skip_zero_tiles = os.environ.get("MLI_SKIP_ZERO_TILES", "1") != "0"
+        # field(elide_outside=True) (the geometry of the fused stage-b train step): the FIELD pass
+        # evaluates only the rays inside the bounds (mli_inside_list); the rays outside it get the
+        # rows their overwritten sdf makes irrelevant and densify() restores the
+        # dense pass for a caller that reads every ray.  MLI_ELIDE_OUTSIDE=0: the dense FIELD
+        self.elide_outside = os.environ.get("MLI_ELIDE_OUTSIDE", "1") != "0"
         # stage-b training: the output layers' dW from per-tile partials the heads forward forms
         # while X3 is in registers (mli_rgb_fwd PQ mode + mli_dw4) instead of X3 through HBM and
         # the THIN split-K GEMM; needs N % 32 == 0 (a 32-sample tile within one ray)
@@ -295,7 +300,7 @@ class RenderEngine:
         out["_keep"] = (w2c, w2l, K, ridx)
         return out
 
-    def _sdf(self, rays, dists, n_per_ray, out, mode=0, grad=None, hess=None, h0=None):
+    def _sdf(self, rays, dists, n_per_ray, out, mode=0, grad=None, hess=None, h0=None, inside=(None, None)):
         R = rays["center"].shape[0]
         enc = None
         if mode == 1:
@@ -306,7 +311,8 @@ class RenderEngine:
                                     L.ptr(dists), L.ptr(rays["outside"]), L.ptr(self.table16), self.levels,
                                     L.ptr(self.wsdf), self.eps, self.grad_den, self.hess_den,
                                     self.cfg.outside_val, 1 if hess is not None else 0, L.ptr(out),
-                                    L.ptr(grad), L.ptr(hess), L.ptr(h0), L.ptr(enc), int(self.active_levels)))
+                                    L.ptr(grad), L.ptr(hess), L.ptr(h0), L.ptr(enc), int(self.active_levels),
+                                    L.ptr(inside[0]), L.ptr(inside[1])))
         return enc
 
     @torch.no_grad()
@@ -346,15 +352,53 @@ class RenderEngine:
         return dists
 
     @torch.no_grad()
-    def field(self, rays, dists, training):
+    def field(self, rays, dists, training, elide_outside=False):
+        """The FIELD pass.  ``elide_outside`` (the geometry of a step whose heads will elide, see
+        elides(); a no-op elsewhere): only the rays inside the bounds are evaluated.  The rays
+        outside them get sdf = outside_val and zero gradients / hessians, and their h0 / enc tiles
+        are not written -- such a state is marked ``elided`` and keeps its lane, and densify()
+        turns it into the dense one."""
         N, R = dists.shape
         S = N * R
         sdf = self._buf("sdf", (N, R))
         grad = self._buf("grad", (N, R, 3))
         hess = self._buf("hess", (N, R, 3)) if training else None
         h0 = self._buf("h0", (S * 256,), torch.float16)
-        enc = self._sdf(rays, dists, N, sdf, mode=1, grad=grad, hess=hess, h0=h0)
-        return dict(sdf=sdf, grad=grad, hess=hess, h0=h0, enc=enc)
+        elided = bool(elide_outside and self.elide_outside and self.elides(N, training))
+        inside = (None, None)
+        if elided:
+            inside = (self._buf("inside_list", (R,), torch.int32), self._buf("n_inside", (1,), torch.int32))
+            # (the heads pad their last workgroup with up to 256 / N - 1 dead rays, processed like
+            # live ones: the outside rays that can be such pads are evaluated too)
+            L.call("mli_inside_list", L.InsideListArgs(R, N, 256 // N - 1, L.ptr(rays["outside"]), L.ptr(inside[0]),
+                                                       L.ptr(inside[1]), self.cfg.outside_val, L.ptr(sdf),
+                                                       L.ptr(grad), L.ptr(hess)))
+        enc = self._sdf(rays, dists, N, sdf, mode=1, grad=grad, hess=hess, h0=h0, inside=inside)
+        return dict(sdf=sdf, grad=grad, hess=hess, h0=h0, enc=enc, elided=elided,
+                    lane=self._bufs if elided else None)
+
+    @torch.no_grad()
+    def densify(self, st):
+        """Make a render state whose FIELD pass skipped the rays outside the bounds (fld
+        ``elided``) the dense one: the dense FIELD pass again, on the state's own rays and dists,
+        into the state's own lane buffers (the rows and tiles of the inside rays are rewritten
+        with the same bits).  For a consumer that reads every ray: the reference output dict, a
+        heads pass that does not elide."""
+        rays, dists, fld = st[0], st[1], st[2]
+        if not fld.get("elided"):
+            return st
+        prev = self._bufs
+        self._bufs = fld["lane"]
+        try:
+            dense = self.field(rays, dists, fld["hess"] is not None)
+        finally:
+            self._bufs = prev
+        for k in ("sdf", "grad", "hess", "h0", "enc"):
+            if (dense[k] is None) != (fld[k] is None) or (dense[k] is not None
+                                                           and dense[k].data_ptr() != fld[k].data_ptr()):
+                raise RuntimeError("densify: the state's lane no longer holds its %s buffer" % k)
+        fld.update(elided=False, lane=None)
+        return st
 
     def pq_mode(self, N, training):
         """The heads run in PQ mode (mli_rgb_fwd weights / q4, mli_dw4) for this render."""
@@ -413,6 +457,8 @@ class RenderEngine:
             masks = self._buf("masks", (nh, 4, S // 32, 64, 4), torch.int32)
         tl = tr = nl = wl = wr = None
         elide = bool(pq and elide and self.elides(N, training))
+        if not elide:
+            self.densify((rays, dists, fld))  # every ray's h0 tiles are read
         if elide:
             # the live rays of this batch, from the weights (device side: the grids stay S / 256
             # and the workgroups past the live tiles return at once)
@@ -564,7 +610,7 @@ class RenderEngine:
         self._bufs["__gen"] = self._bufs.get("__gen", 0) + 1
         rays = self.rays(data["pose"], data["intr"], data["pose_light"], data["ray_idx"], W)
         dists = self.sample(rays, u)
-        fld = self.field(rays, dists, training)
+        fld = self.field(rays, dists, training, elide_outside=elide and s_var is not None)
         hd = self.heads(rays, dists, fld, training, s_var, progress, elide=elide)
         if not composite:
             return rays, dists, fld, hd, None

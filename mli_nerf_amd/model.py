@@ -257,6 +257,7 @@ class Model(torch.nn.Module):
         self.dz3_rebuild = None     # True / False: override RenderEngine.dz3_rebuild (None: its default)
         self.elide_dead_rays = None  # True / False: override RenderEngine.elide_dead_rays (None: its default)
         self.skip_zero_tiles = None  # True / False: override RenderEngine.skip_zero_tiles (None: its default)
+        self.elide_outside = None    # True / False: override RenderEngine.elide_outside (None: its default)
 
     # -------------------------------------------------------------- parameter plumbing
     def _view(self, name, flat=None):
@@ -388,6 +389,8 @@ class Model(torch.nn.Module):
             eng.elide_dead_rays = self.elide_dead_rays
         if self.skip_zero_tiles is not None:
             eng.skip_zero_tiles = self.skip_zero_tiles
+        if self.elide_outside is not None:
+            eng.elide_outside = self.elide_outside
         eng.set_normal_eps(sdf.normal_eps)
         eng.active_levels = int(sdf.active_levels)
         l0 = sdf.mlp.linears[0]
@@ -442,6 +445,8 @@ class Model(torch.nn.Module):
     def outputs(self, st, heads=None):
         """The reference output dict (NeuralLumen/model.py:312-323) of a render state; ``heads``
         = differentiable (rgb, o_r, o_s, o_re) when called under autograd."""
+        if st[2].get("elided"):  # the FIELD pass skipped the rays outside the bounds: every row is read here
+            self.engine.densify(st)
         rays, dists, fld, hd, comp = st
         heads = heads if heads is not None else (comp["rgb"], comp["o_r"], comp["o_s"], comp["o_re"])
         rgb, o_r, o_s, o_re = heads[:4]

@@ -743,7 +743,8 @@ class Trainer:
                 rays = eng.rays(data["pose"], data["intr"], data["pose_light"], data["ray_idx"],
                                 m.image_size_train[1])
                 dists = eng.sample(rays, m.stratified_uniforms(data, u))
-                fld = eng.field(rays, dists, True)
+                # (a step that turns out not to elide densifies the state: RenderEngine.heads)
+                fld = eng.field(rays, dists, True, elide_outside=self.fused_tail)
         finally:
             eng._bufs = prev
         done = torch.cuda.Event()
