@@ -115,6 +115,7 @@ int mli_hashgrid_fwd(const mli_hashgrid_args* a, mli_stream_t s);
  * Weights: `wsdf` from mli_pack (layout MLI_SDF_PACK_*). */
 #define MLI_SDF_MODE_SDF 0   /* sdf only                                                   */
 #define MLI_SDF_MODE_FIELD 1 /* sdf (+outside), grad, hess, h0 frag image                  */
+#define MLI_SDF_MODE_SDF_LISTED 2 /* sdf only, of the rays in inside_list (see below)       */
 typedef struct {
   int mode;
   int R, n_per_ray;
@@ -144,7 +145,13 @@ typedef struct {
    * inside_list[ci / T] * T + ci % T, and a workgroup or wave with ci >= *n_inside * T returns
    * before it gathers anything.  Every buffer is addressed by the original tile / slot, so the
    * sdf / grad / hess rows and the h0 / enc tiles of the rays outside the bounds are NOT written
-   * (mli_inside_list writes those rows; nobody may read those tiles). */
+   * (mli_inside_list writes those rows; nobody may read those tiles).
+   * MLI_SDF_MODE_SDF_LISTED (the sampling rounds of those rays; both arrays required, any
+   * n_per_ray): compact point ci < *n_inside * n_per_ray is sample ci % n_per_ray of ray
+   * inside_list[ci / n_per_ray] (a per-lane load: a 32-point tile may span several rays).  The
+   * grid is the dense call's; a workgroup whose first compact tile is past the bound returns
+   * before it loads the weights.  sdf stays addressed by the original slot k R + r, and the rows of
+   * the rays past the list are NOT written.  MLI_SDF_MODE_SDF takes no list (invalid value). */
   const int32_t* inside_list;
   const int32_t* n_inside;
 } mli_sdf_args;
@@ -165,7 +172,15 @@ int mli_sdf_workspace(const mli_sdf_args* a, int64_t* bytes);
  * n_pad: the heads process up to 256 / N - 1 dead rays as pads of their last workgroup, the first
  * dead rays in ray order (mli_live_rays) -- if such a ray is outside the bounds it is among the
  * first 256 / N - 1 outside rays.  Counting those into n_inside makes the FIELD pass evaluate them
- * as the dense pass does (it runs after this call and overwrites their constant rows). */
+ * as the dense pass does (it runs after this call and overwrites their constant rows).
+ * With dists (and near_ / far_: all three or none) the same call, made before the sampling rounds,
+ * also writes the sample distances of the rays outside the bounds, which the listed rounds
+ * (MLI_SDF_MODE_SDF_LISTED, mli_sample_fine with inside_list) leave alone:
+ *   dists[k][r] = fminf(fmaxf(near_[r] + (((float)k + 0.5f) / (float)N) * (far_[r] - near_[r]),
+ *                             near_[r]), far_[r])      (fp32, each operation rounded, no fma)
+ * finite, nondecreasing in k and inside [near, far]: with sdf = outside_val and zero gradients
+ * the composite weights of such a ray are exactly 0 for any such dists.  The rays counted by
+ * n_pad get the row too; the listed rounds that follow overwrite it with the dense sampler's. */
 struct mli_inside_list_args_s {
   int R, N;
   int n_pad;              /* >= 0 */
@@ -176,6 +191,9 @@ struct mli_inside_list_args_s {
   float* sdf;             /* [N][R] or NULL */
   float* grad;            /* [N][R][3] or NULL */
   float* hess;            /* [N][R][3] or NULL */
+  const float* near_;     /* [R] or NULL */
+  const float* far_;      /* [R] or NULL */
+  float* dists;           /* [N][R] or NULL */
 };
 typedef struct mli_inside_list_args_s mli_inside_list_args;
 int mli_inside_list(const mli_inside_list_args* a, mli_stream_t s);
@@ -201,6 +219,12 @@ typedef struct {
   float inv_s;            /* 64 * 2^h                                                      */
   const float* u_fine;    /* [Nf] midpoint quantiles (torch.linspace semantics, host)       */
   float* fine_out;        /* [Nf][R] */
+  /* Inside rays, optional (both NULL: every ray): the lists of mli_inside_list.  The grid stays
+   * the dense call's; wave rc < *n_inside works on ray inside_list[rc], a workgroup wholly past
+   * the list returns at once, and dists_out / sdf_out / fine_out of the rays past the list are
+   * NOT written (their inputs are never read). */
+  const int32_t* inside_list;
+  const int32_t* n_inside;
 } mli_sample_fine_args;
 int mli_sample_fine(const mli_sample_fine_args* a, mli_stream_t s);
 

@@ -40,7 +40,8 @@ class SdfArgs(C.Structure):
 
 class InsideListArgs(C.Structure):
     _fields_ = [("R", I32), ("N", I32), ("n_pad", I32), ("outside", P), ("inside_list", P), ("n_inside", P),
-                ("outside_val", F32), ("sdf", P), ("grad", P), ("hess", P)]
+                ("outside_val", F32), ("sdf", P), ("grad", P), ("hess", P), ("near_", P), ("far_", P),
+                ("dists", P)]
 
 
 class SampleCoarseArgs(C.Structure):
@@ -50,7 +51,7 @@ class SampleCoarseArgs(C.Structure):
 class SampleFineArgs(C.Structure):
     _fields_ = [("R", I32), ("dists_a", P), ("sdf_a", P), ("Na", I32), ("dists_b", P), ("sdf_b", P),
                 ("Nb", I32), ("dists_out", P), ("sdf_out", P), ("Nf", I32), ("inv_s", F32),
-                ("u_fine", P), ("fine_out", P)]
+                ("u_fine", P), ("fine_out", P), ("inside_list", P), ("n_inside", P)]
 
 
 class RgbFwdArgs(C.Structure):

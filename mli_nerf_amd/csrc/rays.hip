@@ -140,7 +140,21 @@ __global__ __launch_bounds__(FW * 64) void sample_fine_kernel(FineArgs fa) {
   __shared__ float s_ad[FW][FMAX], s_bd[FW][FBMAX], s_md[FW][FMAX], s_ms[FW][FMAX], s_cd[FW][FMAX];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int R = a.R, Na = a.Na, Nb = a.Nb, Nh = Na + Nb;
-  const int r = min((int)(blockIdx.x * FW + w), R - 1);  // tail waves redo the last ray (same values)
+  // tail waves redo the last ray (same values) without storing: every wave reaches the barriers.
+  // With the inside-ray list the rays are the first *n_inside of inside_list, one per wave in
+  // compact order, and a workgroup wholly past them returns (blockIdx and *n_inside: uniform)
+  const int rc = blockIdx.x * FW + w;
+  int r;
+  bool store;
+  if (a.inside_list != nullptr) {
+    const int n_in = min(*a.n_inside, R);
+    if ((int)blockIdx.x * FW >= n_in) return;
+    store = rc < n_in;
+    r = a.inside_list[min(rc, n_in - 1)];
+  } else {
+    store = rc < R;
+    r = min(rc, R - 1);
+  }
   float* ad = s_ad[w];
   float* bd = s_bd[w];
   float* md = s_md[w];
@@ -178,7 +192,6 @@ __global__ __launch_bounds__(FW * 64) void sample_fine_kernel(FineArgs fa) {
     }
     bpos += lo;
   }
-  const bool store = blockIdx.x * FW + w < R;
 #pragma unroll
   for (int e = 0; e < FMAX / 64; ++e) {
     if (lane + 64 * e < Na) {
@@ -729,6 +742,7 @@ extern "C" int mli_sample_fine(const mli_sample_fine_args* a, mli_stream_t s) {
   if (a->R <= 0) return 0;
   if (a->Nf > FBMAX || a->Nb > FBMAX || a->Na < 1 || a->Na + a->Nb > FMAX) return (int)hipErrorInvalidValue;
   if (a->Nf > 0 && a->sdf_out == nullptr) return (int)hipErrorInvalidValue;
+  if ((a->inside_list == nullptr) != (a->n_inside == nullptr)) return (int)hipErrorInvalidValue;
   FineArgs fa;
   fa.a = *a;
   for (int j = 0; j < 64; ++j) fa.u[j] = (j < a->Nf && a->u_fine) ? a->u_fine[j] : 2.0f;
@@ -912,8 +926,9 @@ extern "C" int mli_live_rays(const mli_live_rays_args* a, mli_stream_t s) {
 // ---------------------------------------------------------------------- inside rays
 // mli_inside_list: which rays the FIELD pass must evaluate (include/mli_hip.h).  The first
 // fill_blocks workgroups write the rows FIELD would leave for the rays outside the bounds, one
-// thread per slot k R + r (coalesced over r); the last workgroup scans the R flags in ray order
-// (live_scan_kernel's scan) and writes the list.  The two parts share no data.
+// thread per slot k R + r (coalesced over r) -- and, called before the sampling rounds with
+// dists, the sample distances the listed rounds do not write; the last workgroup scans the R
+// flags in ray order (live_scan_kernel's scan) and writes the list.  The two parts share no data.
 namespace {
 
 __global__ __launch_bounds__(LR_SCAN) void inside_list_kernel(mli_inside_list_args a, int fill_blocks) {
@@ -922,7 +937,16 @@ __global__ __launch_bounds__(LR_SCAN) void inside_list_kernel(mli_inside_list_ar
   if ((int)blockIdx.x < fill_blocks) {
     const size_t i = (size_t)blockIdx.x * LR_SCAN + t;
     if (i >= (size_t)a.R * a.N) return;
-    if (!a.outside[i % a.R]) return;
+    const int r = (int)(i % a.R);
+    if (!a.outside[r]) return;
+    if (a.dists != nullptr) {
+      // the sample distances the listed sampling rounds leave alone (include/mli_hip.h has the
+      // formula; -ffp-contract=off: every operation rounds)
+      const float near = a.near_[r], far = a.far_[r];
+      const float d = near + (((float)(i / a.R) + 0.5f) / (float)a.N) * (far - near);
+      a.dists[i] = fminf(fmaxf(d, near), far);
+    }
+    if (a.sdf == nullptr) return;
     a.sdf[i] = a.outside_val;
     a.grad[3 * i] = 0.0f;
     a.grad[3 * i + 1] = 0.0f;
@@ -965,8 +989,10 @@ extern "C" int mli_inside_list(const mli_inside_list_args* a, mli_stream_t s) {
     return (int)hipErrorInvalidValue;
   if ((a->sdf == nullptr) != (a->grad == nullptr) || (a->hess != nullptr && a->sdf == nullptr))
     return (int)hipErrorInvalidValue;
+  if ((a->dists == nullptr) != (a->near_ == nullptr) || (a->dists == nullptr) != (a->far_ == nullptr))
+    return (int)hipErrorInvalidValue;
   const int64_t S = (int64_t)a->R * a->N;
-  const int fill_blocks = a->sdf ? (int)((S + LR_SCAN - 1) / LR_SCAN) : 0;
+  const int fill_blocks = (a->sdf || a->dists) ? (int)((S + LR_SCAN - 1) / LR_SCAN) : 0;
   hipLaunchKernelGGL(inside_list_kernel, dim3(fill_blocks + 1), dim3(LR_SCAN), 0, (hipStream_t)s, *a, fill_blocks);
   MLI_LAUNCH_CHECK();
 }

@@ -461,13 +461,19 @@ __global__ __launch_bounds__(MLP_WAVES * 64) void field_mlp_kernel(mli_sdf_args 
 }
 
 // SDF only (sampling rounds): one point per lane, encode + layer 0 + sdf head fused.
+// LISTED (MLI_SDF_MODE_SDF_LISTED): the points are those of the first *n_inside rays of
+// inside_list, in compact order (point ci = sample ci % n_per_ray of ray inside_list[ci / n_per_ray],
+// a per-lane load: a tile spans 32 / n_per_ray rays in the fine rounds); the workgroups past them
+// return before the weight load and its barrier (blockIdx and *n_inside only: uniform).
+template <bool LISTED>
 __global__ __launch_bounds__(256) void sdf_kernel(mli_sdf_args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  const int n_total = (LISTED ? min(max(*a.n_inside, 0), a.R) : a.R) * a.n_per_ray;
+  const int n_tiles = (n_total + 31) >> 5;
+  if (LISTED && (int)blockIdx.x * SDF_WAVES >= n_tiles) return;
   load_weights(lds, a.wsdf);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
-  const int n_total = a.R * a.n_per_ray;
-  const int n_tiles = (n_total + 31) >> 5;
   for (int tile = blockIdx.x * SDF_WAVES + wave; tile < n_tiles; tile += gridDim.x * SDF_WAVES) {
     // opaque LDS base: keeps the 64 weight fragments / row constants from being hoisted
     // out of the tile loop (they would pin ~700 registers)
@@ -475,7 +481,8 @@ __global__ __launch_bounds__(256) void sdf_kernel(mli_sdf_args a) {
     const int m = tile * 32 + c;
     const bool valid = m < n_total;
     const int mm = valid ? m : n_total - 1;
-    const int r = mm / a.n_per_ray, k = mm - r * a.n_per_ray;
+    const int rc = mm / a.n_per_ray, k = mm - rc * a.n_per_ray;
+    const int r = LISTED ? a.inside_list[rc] : rc;
     const int slot = k * a.R + r;
     const float d = a.dists[slot];
     // p = c + v * d  (camera.py:314-320; two roundings, no fma)
@@ -1308,10 +1315,17 @@ extern "C" int mli_sdf(const mli_sdf_args* a, mli_stream_t s) {
   const int tiles = (n_total + 31) / 32;
   if (tiles < 1) return 0;
   if (a->mode == MLI_SDF_MODE_SDF) {
-    if (a->inside_list != nullptr || a->n_inside != nullptr) return (int)hipErrorInvalidValue;  // FIELD only
+    if (a->inside_list != nullptr || a->n_inside != nullptr) return (int)hipErrorInvalidValue;  // not this mode
     int blocks = (tiles + SDF_WAVES - 1) / SDF_WAVES;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sdf_kernel, dim3(blocks), dim3(256), LDS_SDF, (hipStream_t)s, *a);
+    hipLaunchKernelGGL(sdf_kernel<false>, dim3(blocks), dim3(256), LDS_SDF, (hipStream_t)s, *a);
+    MLI_LAUNCH_CHECK();
+  }
+  if (a->mode == MLI_SDF_MODE_SDF_LISTED) {  // the dense call's grid, over compact tiles
+    if (a->inside_list == nullptr || a->n_inside == nullptr) return (int)hipErrorInvalidValue;
+    int blocks = (tiles + SDF_WAVES - 1) / SDF_WAVES;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(sdf_kernel<true>, dim3(blocks), dim3(256), LDS_SDF, (hipStream_t)s, *a);
     MLI_LAUNCH_CHECK();
   }
   if (a->h0 == nullptr || a->grad == nullptr) return (int)hipErrorInvalidValue;

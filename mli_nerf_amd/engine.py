@@ -180,6 +180,11 @@ class RenderEngine:
         # rows their overwritten sdf makes irrelevant and densify() restores the
         # dense pass for a caller that reads every ray.  MLI_ELIDE_OUTSIDE=0: the dense FIELD
         self.elide_outside = os.environ.get("MLI_ELIDE_OUTSIDE", "1") != "0"
+        # ... and the hierarchical sampling rounds before it run only for those rays too: the list
+        # is built before sample() (inside_rays) and serves both; the rays outside the bounds get
+        # evenly spaced dists in [near, far], which their zero weights make irrelevant (DESIGN.md
+        # §9.14).  No effect with elide_outside off.  MLI_ELIDE_OUTSIDE_SAMPLING=0: the dense sampler
+        self.elide_outside_sampling = os.environ.get("MLI_ELIDE_OUTSIDE_SAMPLING", "1") != "0"
         # stage-b training: the output layers' dW from per-tile partials the heads forward forms
         # while X3 is in registers (mli_rgb_fwd PQ mode + mli_dw4) instead of X3 through HBM and
         # the THIN split-K GEMM; needs N % 32 == 0 (a 32-sample tile within one ray)
@@ -316,18 +321,43 @@ class RenderEngine:
         return enc
 
     @torch.no_grad()
-    def sample(self, rays, u=None):
-        """sample_dists_all (neuralangelo/model.py:449-465) -> dists [N][R]."""
+    def inside_rays(self, rays, training, elide=True):
+        """The inside-ray list of a pass whose sampler and FIELD pass both skip the rays outside
+        the bounds, built before sample(): one mli_inside_list call that also writes those rays'
+        FIELD rows and their dists.  None where that does not apply (elides(), the two switches):
+        sample() and field() then run as without it."""
+        N = self.cfg.n_samples
+        if not (elide and self.elide_outside and self.elide_outside_sampling and self.elides(N, training)):
+            return None
+        R = rays["center"].shape[0]
+        inside = (self._buf("inside_list", (R,), torch.int32), self._buf("n_inside", (1,), torch.int32))
+        hess = self._buf("hess", (N, R, 3)) if training else None
+        # (the heads pad their last workgroup with up to 256 / N - 1 dead rays, processed like
+        # live ones: the outside rays that can be such pads are sampled and evaluated too)
+        L.call("mli_inside_list", L.InsideListArgs(
+            R, N, 256 // N - 1, L.ptr(rays["outside"]), L.ptr(inside[0]), L.ptr(inside[1]), self.cfg.outside_val,
+            L.ptr(self._buf("sdf", (N, R))), L.ptr(self._buf("grad", (N, R, 3))), L.ptr(hess),
+            L.ptr(rays["near"]), L.ptr(rays["far"]), L.ptr(self._buf("dists", (N, R)))))
+        return inside
+
+    @torch.no_grad()
+    def sample(self, rays, u=None, inside=None):
+        """sample_dists_all (neuralangelo/model.py:449-465) -> dists [N][R].  ``inside`` (the
+        lists of inside_rays()): the sdf and fine rounds run for the listed rays only; the
+        intermediate buffers of the other rays are neither written nor read, and their dists are
+        the rows inside_rays() wrote."""
         cfg = self.cfg
         R = rays["center"].shape[0]
         Nc, Nf, H = cfg.n_coarse, cfg.n_fine, cfg.n_hier
         N = cfg.n_samples
+        lst = (None, None) if inside is None else (L.ptr(inside[0]), L.ptr(inside[1]))
+        mode = 0 if inside is None else 2
         d0 = self._buf("d_coarse", (Nc, R))
         uu = None if u is None else u.reshape(R, Nc).contiguous()
         L.call("mli_sample_coarse", L.SampleCoarseArgs(L.ptr(rays["near"]), L.ptr(rays["far"]), L.ptr(uu),
                                                        R, Nc, L.ptr(d0)))
         s0 = self._buf("s_coarse", (Nc, R))
-        self._sdf(rays, d0, Nc, s0)
+        self._sdf(rays, d0, Nc, s0, mode=mode, inside=inside or (None, None))
         da, sa, na = d0, s0, Nc
         db = sb = None
         nb = 0
@@ -337,36 +367,40 @@ class RenderEngine:
             f = self._buf("d_f%d" % (h & 1), (Nf, R))
             L.call("mli_sample_fine", L.SampleFineArgs(R, L.ptr(da), L.ptr(sa), na, L.ptr(db), L.ptr(sb), nb,
                                                        L.ptr(dm), L.ptr(sm), Nf, float(64 * 2 ** h),
-                                                       C.cast(self.u_fine, C.c_void_p), L.ptr(f)))
+                                                       C.cast(self.u_fine, C.c_void_p), L.ptr(f), *lst))
             sf = None
             if h < H - 1:
                 sf = self._buf("s_f%d" % (h & 1), (Nf, R))
-                self._sdf(rays, f, Nf, sf)
+                self._sdf(rays, f, Nf, sf, mode=mode, inside=inside or (None, None))
             if self.trace is not None:
                 self.trace.append(dict(merged=dm.clone(), merged_sdf=sm.clone(), fine=f.clone(),
                                        fine_sdf=None if sf is None else sf.clone()))
             da, sa, na, db, sb, nb = dm, sm, na + nb, f, sf, Nf
         dists = self._buf("dists", (N, R))
         L.call("mli_sample_fine", L.SampleFineArgs(R, L.ptr(da), None, na, L.ptr(db), None, nb, L.ptr(dists),
-                                                   None, 0, 0.0, None, None))
+                                                   None, 0, 0.0, None, None, *lst))
         return dists
 
     @torch.no_grad()
-    def field(self, rays, dists, training, elide_outside=False):
+    def field(self, rays, dists, training, elide_outside=False, inside=None, u=None):
         """The FIELD pass.  ``elide_outside`` (the geometry of a step whose heads will elide, see
         elides(); a no-op elsewhere): only the rays inside the bounds are evaluated.  The rays
         outside them get sdf = outside_val and zero gradients / hessians, and their h0 / enc tiles
         are not written -- such a state is marked ``elided`` and keeps its lane, and densify()
-        turns it into the dense one."""
+        turns it into the dense one.  ``inside``: the lists of inside_rays(), which sample() ran
+        on too (the pass is then elided whatever ``elide_outside`` says, and the state keeps the
+        stratified uniforms ``u`` for densify() to re-run the dense sampler)."""
         N, R = dists.shape
         S = N * R
         sdf = self._buf("sdf", (N, R))
         grad = self._buf("grad", (N, R, 3))
         hess = self._buf("hess", (N, R, 3)) if training else None
         h0 = self._buf("h0", (S * 256,), torch.float16)
-        elided = bool(elide_outside and self.elide_outside and self.elides(N, training))
-        inside = (None, None)
-        if elided:
+        elided = inside is not None or bool(elide_outside and self.elide_outside and self.elides(N, training))
+        sampled = inside is not None
+        if not elided:
+            inside = (None, None)
+        elif not sampled:
             inside = (self._buf("inside_list", (R,), torch.int32), self._buf("n_inside", (1,), torch.int32))
             # (the heads pad their last workgroup with up to 256 / N - 1 dead rays, processed like
             # live ones: the outside rays that can be such pads are evaluated too)
@@ -375,7 +409,7 @@ class RenderEngine:
                                                        L.ptr(grad), L.ptr(hess)))
         enc = self._sdf(rays, dists, N, sdf, mode=1, grad=grad, hess=hess, h0=h0, inside=inside)
         return dict(sdf=sdf, grad=grad, hess=hess, h0=h0, enc=enc, elided=elided,
-                    lane=self._bufs if elided else None)
+                    lane=self._bufs if elided else None, sampling_elided=sampled, u=u if sampled else None)
 
     @torch.no_grad()
     def densify(self, st):
@@ -383,21 +417,30 @@ class RenderEngine:
         ``elided``) the dense one: the dense FIELD pass again, on the state's own rays and dists,
         into the state's own lane buffers (the rows and tiles of the inside rays are rewritten
         with the same bits).  For a consumer that reads every ray: the reference output dict, a
-        heads pass that does not elide."""
+        heads pass that does not elide.  A state whose sampling rounds skipped those rays too
+        (``sampling_elided``) first gets the dense sampler again, on the pass's own stratified
+        uniforms, into the same ``dists`` buffer."""
         rays, dists, fld = st[0], st[1], st[2]
         if not fld.get("elided"):
             return st
         prev = self._bufs
         self._bufs = fld["lane"]
         try:
-            dense = self.field(rays, dists, fld["hess"] is not None)
+            dense = dict(dists=dists)
+            if fld.get("sampling_elided"):
+                u = fld["u"]
+                if u is not None:  # allocated on the prefetch stream, read here
+                    u.record_stream(torch.cuda.current_stream(u.device))
+                dense["dists"] = self.sample(rays, u)
+            dense.update(self.field(rays, dists, fld["hess"] is not None))
         finally:
             self._bufs = prev
-        for k in ("sdf", "grad", "hess", "h0", "enc"):
-            if (dense[k] is None) != (fld[k] is None) or (dense[k] is not None
-                                                           and dense[k].data_ptr() != fld[k].data_ptr()):
+        for k in ("dists", "sdf", "grad", "hess", "h0", "enc"):
+            have = dists if k == "dists" else fld[k]
+            if (dense[k] is None) != (have is None) or (dense[k] is not None
+                                                        and dense[k].data_ptr() != have.data_ptr()):
                 raise RuntimeError("densify: the state's lane no longer holds its %s buffer" % k)
-        fld.update(elided=False, lane=None)
+        fld.update(elided=False, lane=None, sampling_elided=False, u=None)
         return st
 
     def pq_mode(self, N, training):
@@ -609,8 +652,10 @@ class RenderEngine:
         heads()."""
         self._bufs["__gen"] = self._bufs.get("__gen", 0) + 1
         rays = self.rays(data["pose"], data["intr"], data["pose_light"], data["ray_idx"], W)
-        dists = self.sample(rays, u)
-        fld = self.field(rays, dists, training, elide_outside=elide and s_var is not None)
+        elide_outside = elide and s_var is not None
+        inside = self.inside_rays(rays, training, elide_outside)
+        dists = self.sample(rays, u, inside=inside)
+        fld = self.field(rays, dists, training, elide_outside=elide_outside, inside=inside, u=u)
         hd = self.heads(rays, dists, fld, training, s_var, progress, elide=elide)
         if not composite:
             return rays, dists, fld, hd, None

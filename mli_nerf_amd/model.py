@@ -258,6 +258,8 @@ class Model(torch.nn.Module):
         self.elide_dead_rays = None  # True / False: override RenderEngine.elide_dead_rays (None: its default)
         self.skip_zero_tiles = None  # True / False: override RenderEngine.skip_zero_tiles (None: its default)
         self.elide_outside = None    # True / False: override RenderEngine.elide_outside (None: its default)
+        # True / False: override RenderEngine.elide_outside_sampling (None: its default)
+        self.elide_outside_sampling = None
 
     # -------------------------------------------------------------- parameter plumbing
     def _view(self, name, flat=None):
@@ -391,6 +393,8 @@ class Model(torch.nn.Module):
             eng.skip_zero_tiles = self.skip_zero_tiles
         if self.elide_outside is not None:
             eng.elide_outside = self.elide_outside
+        if self.elide_outside_sampling is not None:
+            eng.elide_outside_sampling = self.elide_outside_sampling
         eng.set_normal_eps(sdf.normal_eps)
         eng.active_levels = int(sdf.active_levels)
         l0 = sdf.mlp.linears[0]

@@ -742,9 +742,12 @@ class Trainer:
                 eng.use_lane(lane, geometry_only=True)
                 rays = eng.rays(data["pose"], data["intr"], data["pose_light"], data["ray_idx"],
                                 m.image_size_train[1])
-                dists = eng.sample(rays, m.stratified_uniforms(data, u))
+                uu = m.stratified_uniforms(data, u)
+                # one inside-ray list for the sampling rounds and the FIELD pass
                 # (a step that turns out not to elide densifies the state: RenderEngine.heads)
-                fld = eng.field(rays, dists, True, elide_outside=self.fused_tail)
+                inside = eng.inside_rays(rays, True, self.fused_tail)
+                dists = eng.sample(rays, uu, inside=inside)
+                fld = eng.field(rays, dists, True, elide_outside=self.fused_tail, inside=inside, u=uu)
         finally:
             eng._bufs = prev
         done = torch.cuda.Event()
