@@ -876,37 +876,61 @@ __global__ __launch_bounds__(4 * LR_RAYS) void live_flags_kernel(mli_live_rays_a
   }
 }
 
-__global__ __launch_bounds__(LR_SCAN) void live_scan_kernel(mli_live_rays_args a) {
-  __shared__ int sums[LR_SCAN];
+// The compaction scan of mli_live_rays, mli_inside_list and mli_live_tiles: one workgroup of LR_SCAN
+// threads over n rays.  Thread t takes a contiguous chunk of rays in ray order; flag(r) != 0 keeps
+// ray r (TILES: its set bits are counted too).  After the LR_SCAN-wide inclusive scan(s) in LDS
+// (1 + TILES int[LR_SCAN] arrays), emit(r, f, pos, before, wbefore) runs for every ray: pos is its
+// compact position -- the kept rays first, then the others, each in ascending order --, before the
+// kept rays below r and wbefore the set flag bits of the rays below r.  kept / bits: the totals.
+template <bool TILES, class Flag, class Emit>
+MLI_FI void compact_scan(int n, Flag flag, Emit emit, int& kept, int& bits) {
+  __shared__ int sums[1 + TILES][LR_SCAN];
   const int t = threadIdx.x;
-  const int T = a.N / 32, G = 256 / a.N;
   // thread t: rays [r0, r1), a contiguous chunk in ray order
-  const int per = (a.R + LR_SCAN - 1) / LR_SCAN;
-  const int r0 = min(t * per, a.R), r1 = min(r0 + per, a.R);
-  int cnt = 0;
-  for (int r = r0; r < r1; ++r) cnt += a.flags[r];
-  sums[t] = cnt;
-  __syncthreads();
-  // inclusive scan (Hillis-Steele; integer sums: any order gives the same counts)
-  for (int o = 1; o < LR_SCAN; o <<= 1) {
-    const int v = t >= o ? sums[t - o] : 0;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  const int L = sums[LR_SCAN - 1];
-  int before = sums[t] - cnt;  // live rays before ray r0
+  const int per = (n + LR_SCAN - 1) / LR_SCAN;
+  const int r0 = min(t * per, n), r1 = min(r0 + per, n);
+  int cnt = 0, wcnt = 0;
   for (int r = r0; r < r1; ++r) {
-    const int live = a.flags[r];
-    // compact ray position: the live rays first, then the dead ones, each in ascending order
-    const int pos = live ? before : L + (r - before);
-    for (int i = 0; i < T; ++i) {
-      a.tile_list[pos * T + i] = r * T + i;
-      a.tile_rank[r * T + i] = before * T + (live ? i : 0);
-    }
-    before += live;
+    const uint32_t f = flag(r);
+    cnt += f != 0;
+    if (TILES) wcnt += __popc(f);
   }
-  if (t == 0) {
+  sums[0][t] = cnt;
+  if (TILES) sums[TILES][t] = wcnt;
+  __syncthreads();
+  // inclusive scans (Hillis-Steele; integer sums: any order gives the same counts)
+  for (int o = 1; o < LR_SCAN; o <<= 1) {
+    const int v = t >= o ? sums[0][t - o] : 0, wv = TILES && t >= o ? sums[TILES][t - o] : 0;
+    __syncthreads();
+    sums[0][t] += v;
+    if (TILES) sums[TILES][t] += wv;
+    __syncthreads();
+  }
+  kept = sums[0][LR_SCAN - 1];
+  bits = TILES ? sums[TILES][LR_SCAN - 1] : 0;
+  int before = sums[0][t] - cnt;                      // kept rays before ray r0
+  int wbefore = TILES ? sums[TILES][t] - wcnt : 0;    // flag bits before ray r0 (kept rays keep their order)
+  for (int r = r0; r < r1; ++r) {
+    const uint32_t f = flag(r);
+    emit(r, f, f != 0 ? before : kept + (r - before), before, wbefore);
+    before += f != 0;
+    if (TILES) wbefore += __popc(f);
+  }
+}
+
+__global__ __launch_bounds__(LR_SCAN) void live_scan_kernel(mli_live_rays_args a) {
+  const int T = a.N / 32, G = 256 / a.N;
+  int L, none;
+  compact_scan<false>(
+      a.R, [&](int r) MLI_LAMBDA_FI { return (uint32_t)a.flags[r]; },
+      [&](int r, uint32_t live, int pos, int before, int) MLI_LAMBDA_FI {
+        for (int i = 0; i < T; ++i) {
+          a.tile_list[pos * T + i] = r * T + i;
+          a.tile_rank[r * T + i] = before * T + (live ? i : 0);
+        }
+      },
+      L, none);
+  if (threadIdx.x == 0) {
     a.tile_rank[a.R * T] = L * T;
     a.n_live_tiles[0] = (L + G - 1) / G * G * T;
   }
@@ -932,7 +956,6 @@ extern "C" int mli_live_rays(const mli_live_rays_args* a, mli_stream_t s) {
 namespace {
 
 __global__ __launch_bounds__(LR_SCAN) void inside_list_kernel(mli_inside_list_args a, int fill_blocks) {
-  __shared__ int sums[LR_SCAN];
   const int t = threadIdx.x;
   if ((int)blockIdx.x < fill_blocks) {
     const size_t i = (size_t)blockIdx.x * LR_SCAN + t;
@@ -958,27 +981,10 @@ __global__ __launch_bounds__(LR_SCAN) void inside_list_kernel(mli_inside_list_ar
     }
     return;
   }
-  // thread t: rays [r0, r1), a contiguous chunk in ray order
-  const int per = (a.R + LR_SCAN - 1) / LR_SCAN;
-  const int r0 = min(t * per, a.R), r1 = min(r0 + per, a.R);
-  int cnt = 0;
-  for (int r = r0; r < r1; ++r) cnt += a.outside[r] == 0;
-  sums[t] = cnt;
-  __syncthreads();
-  // inclusive scan (Hillis-Steele; integer sums: any order gives the same counts)
-  for (int o = 1; o < LR_SCAN; o <<= 1) {
-    const int v = t >= o ? sums[t - o] : 0;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  const int n_in = sums[LR_SCAN - 1];
-  int before = sums[t] - cnt;  // inside rays before ray r0
-  for (int r = r0; r < r1; ++r) {
-    const int in = a.outside[r] == 0;
-    a.inside_list[in ? before : n_in + (r - before)] = r;
-    before += in;
-  }
+  int n_in, none;
+  compact_scan<false>(
+      a.R, [&](int r) MLI_LAMBDA_FI { return (uint32_t)(a.outside[r] == 0); },
+      [&](int r, uint32_t, int pos, int, int) MLI_LAMBDA_FI { a.inside_list[pos] = r; }, n_in, none);
   if (t == 0) a.n_inside[0] = min(n_in + a.n_pad, a.R);  // the first n_pad outside rays follow the inside ones
 }
 
@@ -1011,52 +1017,25 @@ constexpr int LT_WAVES = LR_SCAN / 64;  // the pass's workgroups have the scan's
 // One workgroup of LR_SCAN threads.  The flags come from other workgroups of the same launch
 // (last-ticket mode): read at agent scope, past this CU's and XCD's caches.
 MLI_FI void live_tiles_scan(const mli_live_tiles_args& a) {
-  __shared__ int sums[2][LR_SCAN];
-  const int t = threadIdx.x;
   const int R = a.comp.R, N = a.comp.N;
   const int T = N / 32, G = 256 / N;
-  auto flag_of = [&](int r) MLI_LAMBDA_FI {
-    return (uint32_t)__hip_atomic_load(a.flags + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  // thread t: rays [r0, r1), a contiguous chunk in ray order
-  const int per = (R + LR_SCAN - 1) / LR_SCAN;
-  const int r0 = min(t * per, R), r1 = min(r0 + per, R);
-  int cnt = 0, wcnt = 0;
-  for (int r = r0; r < r1; ++r) {
-    const uint32_t f = flag_of(r);
-    cnt += f != 0;
-    wcnt += __popc(f);
-  }
-  sums[0][t] = cnt;
-  sums[1][t] = wcnt;
-  __syncthreads();
-  // inclusive scans (Hillis-Steele; integer sums: any order gives the same counts)
-  for (int o = 1; o < LR_SCAN; o <<= 1) {
-    const int v = t >= o ? sums[0][t - o] : 0, wv = t >= o ? sums[1][t - o] : 0;
-    __syncthreads();
-    sums[0][t] += v;
-    sums[1][t] += wv;
-    __syncthreads();
-  }
-  const int L = sums[0][LR_SCAN - 1], W = sums[1][LR_SCAN - 1];
-  int before = sums[0][t] - cnt;    // live rays before ray r0
-  int wbefore = sums[1][t] - wcnt;  // nonzero tiles before ray r0 (live rays keep their order)
-  for (int r = r0; r < r1; ++r) {
-    const uint32_t f = flag_of(r);
-    const int live = f != 0;
-    // compact ray position: the live rays first, then the dead ones, each in ascending order
-    const int pos = live ? before : L + (r - before);
-    for (int i = 0; i < T; ++i) {
-      const int below = wbefore + __popc(f & ((1u << i) - 1u));
-      a.tile_list[pos * T + i] = r * T + i;
-      a.tile_rank[r * T + i] = before * T + (live ? i : 0);
-      a.wtile_rank[pos * T + i] = live ? below : W;
-      if ((f >> i) & 1u) a.wtile_list[below] = pos * T + i;
-    }
-    before += live;
-    wbefore += __popc(f);
-  }
-  if (t == 0) {
+  int L, W;  // live rays, nonzero tiles
+  compact_scan<true>(
+      R,
+      [&](int r) MLI_LAMBDA_FI {
+        return (uint32_t)__hip_atomic_load(a.flags + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      },
+      [&](int r, uint32_t f, int pos, int before, int wbefore) MLI_LAMBDA_FI {
+        for (int i = 0; i < T; ++i) {
+          const int below = wbefore + __popc(f & ((1u << i) - 1u));
+          a.tile_list[pos * T + i] = r * T + i;
+          a.tile_rank[r * T + i] = before * T + (f != 0 ? i : 0);
+          a.wtile_rank[pos * T + i] = f != 0 ? below : W;
+          if ((f >> i) & 1u) a.wtile_list[below] = pos * T + i;
+        }
+      },
+      L, W);
+  if (threadIdx.x == 0) {
     a.tile_rank[R * T] = L * T;
     a.wtile_rank[R * T] = W;
     a.n_live_tiles[0] = (L + G - 1) / G * G * T;

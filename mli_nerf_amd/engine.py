@@ -12,9 +12,11 @@ Reference call stack mirrored: NeuralLumen/model.py:113-131 (forward),
 :232-336 (render_rays_lumen), :338-403 (render_rays_object_lumen),
 neuralangelo/model.py:449-515 (sampling, NeuS alphas).
 """
+import contextlib
 import ctypes as C
 import math
 import os
+import types
 
 import numpy as np
 import torch
@@ -60,43 +62,108 @@ GEOMETRY_BUFS = frozenset(["center", "ray_unit", "ray_norm", "pts_light", "near"
                            "s_f1", "dists", "sdf", "grad", "hess", "h0", "enc5", "inside_list", "n_inside"])
 
 
-class _GeometryLane(dict):
-    """A lane's buffer set whose geometry buffers (GEOMETRY_BUFS) are its own and every other
-    buffer (the heads' activations, the backward's dZ images and dW slabs, the loss scratch, the
-    render generation) lives in one set shared by all such lanes.  The training prefetch renders
-    only the geometry of batch k+1 / k+2 into its lane while step k runs, and the steps run one
-    after another on the main stream, so one set of step buffers serves every lane (VERDICT r4
-    item 7: ~7.5 GiB per lane at 4096 x 128 otherwise)."""
+class _Lane:
+    """One scratch-buffer set.  A full lane keeps every buffer in ``own`` (its ``step`` is ``own``); a
+    geometry-only lane keeps only its geometry buffers (GEOMETRY_BUFS) there and every other one (the
+    heads' activations, the backward's dZ images and dW slabs, the loss scratch, the render
+    generation) in ``step``, the one set shared by all such lanes: the training prefetch renders only
+    the geometry of batch k+1 / k+2 into its lane while step k runs, and the steps run one after
+    another on the main stream (~7.5 GiB per lane at 4096 x 128 otherwise)."""
 
-    def __init__(self, shared):
-        super().__init__()
-        self.shared = shared
+    def __init__(self, shared=None):
+        self.own = {}
+        self.step = self.own if shared is None else shared
 
-    def _d(self, k):
-        return self if k in GEOMETRY_BUFS else self.shared
+    def of(self, name):   # the dict that holds buffer ``name``
+        return self.own if name in GEOMETRY_BUFS else self.step
 
-    def __getitem__(self, k):
-        d = self._d(k)
-        return dict.__getitem__(d, k) if d is self else d[k]
 
-    def __setitem__(self, k, v):
-        d = self._d(k)
-        if d is self:
-            dict.__setitem__(self, k, v)
-        else:
-            d[k] = v
+class _Lanes:
+    """The scratch-buffer lanes of an engine (which sets ``device``) and the current one."""
 
-    def __contains__(self, k):
-        d = self._d(k)
-        return dict.__contains__(d, k) if d is self else k in d
+    def __init__(self):
+        self._lanes = {0: _Lane()}
+        self._lane = self._lanes[0]  # the current lane (see use_lane)
+        self._shared_step = {}       # the step buffers shared by the geometry-only lanes
 
-    def get(self, k, default=None):
-        d = self._d(k)
-        return dict.get(d, k, default) if d is self else d.get(k, default)
+    def _lane_named(self, lane, geometry_only):
+        if lane not in self._lanes:
+            self._lanes[lane] = _Lane(self._shared_step if geometry_only else None)
+        found = self._lanes[lane]
+        if geometry_only != (found.step is not found.own):
+            raise RuntimeError("engine lane %r was created with geometry_only=%s" % (lane, not geometry_only))
+        return found
 
-    def pop(self, k, *default):
-        d = self._d(k)
-        return dict.pop(d, k, *default) if d is self else d.pop(k, *default)
+    def use_lane(self, lane, geometry_only=False):
+        """Switch to scratch-buffer set ``lane``: renders in flight on different streams (the
+        pipelined inference chunks, Model.inference; with ``geometry_only`` the training prefetch,
+        Trainer.prefetch: _Lane) each own one, reused only on its own stream: stream order protects it."""
+        self._lane = self._lane_named(lane, geometry_only)
+
+    @contextlib.contextmanager
+    def lane(self, lane, geometry_only=False):
+        """use_lane() for a ``with`` block: the previous lane is current again afterwards, after an
+        exception too.  ``lane`` may be a lane itself (a render state's fld["lane"])."""
+        prev = self._lane
+        self._lane = lane if isinstance(lane, _Lane) else self._lane_named(lane, geometry_only)
+        try:
+            yield
+        finally:
+            self._lane = prev
+
+    def _buf(self, name, shape, dtype=torch.float32):
+        """Buffer ``name`` of the current lane, (re)allocated on ``self.device`` when too small."""
+        bufs = self._lane.of(name)
+        t = bufs.get(name)
+        n = math.prod(shape)
+        if t is None or t.numel() < n or t.dtype != dtype:
+            t = bufs[name] = torch.empty(n, dtype=dtype, device=self.device)
+        return t[:n].view(*shape)
+
+    @property
+    def _bufs(self):
+        """The current lane's buffers by name, read-only (tests and tools look buffers up here)."""
+        lane = self._lane
+        return types.MappingProxyType(lane.own if lane.step is lane.own else {**lane.step, **lane.own})
+
+
+# The A/B switches: (attribute, environment variable, default, kind).  An engine reads the environment
+# when it is built; a Model attribute of the same name that is not None overrides it (Model.prepare).
+SWITCHES = (
+    # mli_wgrad classes (bit mask) whose k-slices are reduced through partial slabs + an
+    # ordered sum (the deterministic mode's) instead of fp32 atomics outside that mode too:
+    # WIDE (its 80 k-slices x 3 x 256 x 304 atomic adds burst at the end of the launch).
+    # Measured (profiles/r5/slabs, same box): WIDE 0.299 -> 0.265 ms; BIG 0.831 -> 0.840 and
+    # THIN 0.143 -> 0.204 ms the other way, stage a slower with its 5S job on slabs.
+    ("wgrad_slab_classes", "MLI_WGRAD_SLABS", 2, int),
+    # backward() given dz4 (the fused train step): mli_rgb_bwd does not store dZ3 and the
+    # layer-3 dW jobs rebuild it from dz4, the ReLU mask and W4^T (mli_wgrad_job.rb_*),
+    # bit-identical; MLI_DZ3_REBUILD=0: the stored image (A/B runs)
+    ("dz3_rebuild", "MLI_DZ3_REBUILD", True, bool),
+    # heads(elide=True) (the fused stage-b train step): the heads, their backward and the weight
+    # gradients run only for the rays with a composite weight != 0 (mli_live_rays),
+    # value-identical; MLI_ELIDE_DEAD=0: the dense path (A/B runs)
+    ("elide_dead_rays", "MLI_ELIDE_DEAD", True, bool),
+    # with the elision: the weights and every live list come from one pass over the rays
+    # (mli_live_tiles) instead of mli_composite_fwd + mli_live_rays; 1: the scan is a second
+    # launch, 2: the last workgroup of the pass scans (one launch), 0: the three launches
+    # (A/B runs; DESIGN.md §9.12 has the measurements behind the default)
+    ("live_tiles_pass", "MLI_LIVE_TILES_PASS", 1, int),
+    # ... and the dW kernels stream only the tiles with a nonzero composite weight (a tile of
+    # a live ray whose weights are all zero adds +-0 to every sum); MLI_SKIP_ZERO_TILES=0:
+    # every tile of the live rays (A/B runs).  Needs the lists of mli_live_tiles.
+    ("skip_zero_tiles", "MLI_SKIP_ZERO_TILES", True, bool),
+    # the geometry of the fused stage-b train step (inside_rays): the FIELD pass evaluates only
+    # the rays inside the bounds (mli_inside_list); the rays outside it get the rows their
+    # overwritten sdf makes irrelevant (DESIGN.md §9.13) and densify() restores the dense pass
+    # for a caller that reads every ray.  MLI_ELIDE_OUTSIDE=0: the dense FIELD
+    ("elide_outside", "MLI_ELIDE_OUTSIDE", True, bool),
+    # ... and the hierarchical sampling rounds before it run only for those rays too: the one
+    # list serves both; the rays outside the bounds get evenly spaced dists in [near, far],
+    # which their zero weights make irrelevant (DESIGN.md §9.14).  No effect with elide_outside
+    # off.  MLI_ELIDE_OUTSIDE_SAMPLING=0: the dense sampler
+    ("elide_outside_sampling", "MLI_ELIDE_OUTSIDE_SAMPLING", True, bool),
+)
 
 
 # stage-b weight-gradient classes in launch order and the head layers each one completes
@@ -105,12 +172,20 @@ GRAD_CLASSES = ("out", "big", "wide")
 GRAD_CLASS_LAYERS = {"out": (4,), "big": (1, 2, 3), "wide": (0,)}
 
 
+def _head_dw_sizes(k_out):   # (rows, packed columns) of the dW of the five layers of a k_out-output head
+    return [(256, layout.K0)] + [(256, 256)] * 3 + [(k_out, 256)]
+
+
+def _dw_numel(sizes):   # elements of a split-K accumulator: a dW and a db per layer
+    return sum(m * k + m for m, k in sizes)
+
+
 def _to_device_structs(structs, device):
     raw = b"".join(bytes(s) for s in structs)
     return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
 
 
-class RenderEngine:
+class RenderEngine(_Lanes):
     """``stage`` 'b': LumenRGB 'rgb_r_s' (three heads, frozen geometry); 'a': mode 'rgb' (one
     head) with the geometry trained -- hash table, SDF MLP and s_var (backward_a)."""
 
@@ -142,9 +217,7 @@ class RenderEngine:
         self._kmaps = []  # keep host kmap tensors alive
         self.tlayout, self.n_train = layout.trainable_layout(stage)
         self.toff = {name: (off, shape) for name, shape, off in self.tlayout}
-        self._lanes = {0: {}}
-        self._bufs = self._lanes[0]  # the current lane's scratch buffers (see use_lane)
-        self._shared_step = None     # the step buffers shared by the geometry-only lanes
+        _Lanes.__init__(self)
         self.gate_wgrad, self.gate_event = False, None  # event before the dW launches (Trainer.prefetch)
         self.u_fine = (C.c_float * 64)(*(layout.u_fine(cfg.n_fine) + [2.0] * (64 - cfg.n_fine)))
         self._pack_descs = None
@@ -152,39 +225,9 @@ class RenderEngine:
         # fixed-order reductions instead of fp32 atomics in mli_wgrad / mli_hash_bwd:
         # bit-reproducible gradients at the cost of partial-slab traffic
         self.deterministic = False
-        # mli_wgrad classes (bit mask) whose k-slices are reduced through partial slabs + an
-        # ordered sum (the deterministic mode's) instead of fp32 atomics outside that mode too:
-        # WIDE (its 80 k-slices x 3 x 256 x 304 atomic adds burst at the end of the launch).
-        # Measured (profiles/r5/slabs, same box): WIDE 0.299 -> 0.265 ms; BIG 0.831 -> 0.840 and
-        # THIN 0.143 -> 0.204 ms the other way, stage a slower with its 5S job on slabs.
-        self.wgrad_slab_classes = int(os.environ.get("MLI_WGRAD_SLABS", "2"))
-        # backward() given dz4 (the fused train step): mli_rgb_bwd does not store dZ3 and the
-        # layer-3 dW jobs rebuild it from dz4, the ReLU mask and W4^T (mli_wgrad_job.rb_*),
-        # bit-identical; MLI_DZ3_REBUILD=0: the stored image (A/B runs)
-        self.dz3_rebuild = os.environ.get("MLI_DZ3_REBUILD", "1") != "0"
-        # heads(elide=True) (the fused stage-b train step): the heads, their backward and the weight
-        # gradients run only for the rays with a composite weight != 0 (mli_live_rays),
-        # value-identical; MLI_ELIDE_DEAD=0: the dense path (A/B runs)
-        self.elide_dead_rays = os.environ.get("MLI_ELIDE_DEAD", "1") != "0"
-        # with the elision: the weights and every live list come from one pass over the rays
-        # (mli_live_tiles) instead of mli_composite_fwd + mli_live_rays; 1: the scan is a second
-        # launch, 2: the last workgroup of the pass scans (one launch), 0: the three launches
-        # (A/B runs; DESIGN.md §9.12 has the measurements behind the default)
-        self.live_tiles_pass = int(os.environ.get("MLI_LIVE_TILES_PASS", "1"))
-        # ... and the dW kernels stream only the tiles with a nonzero composite weight (a tile of
-        # a live ray whose weights are all zero adds +-0 to every sum); MLI_SKIP_ZERO_TILES=0:
-        # every tile of the live rays (A/B runs).  Needs the lists of mli_live_tiles.
-        self.skip_zero_tiles = os.environ.get("MLI_SKIP_ZERO_TILES", "1") != "0"
-        # field(elide_outside=True) (the geometry of the fused stage-b train step): the FIELD pass
-        # evaluates only the rays inside the bounds (mli_inside_list); the rays outside it get the
-        # rows their overwritten sdf makes irrelevant and densify() restores the
-        # dense pass for a caller that reads every ray.  MLI_ELIDE_OUTSIDE=0: the dense FIELD
-        self.elide_outside = os.environ.get("MLI_ELIDE_OUTSIDE", "1") != "0"
-        # ... and the hierarchical sampling rounds before it run only for those rays too: the list
-        # is built before sample() (inside_rays) and serves both; the rays outside the bounds get
-        # evenly spaced dists in [near, far], which their zero weights make irrelevant (DESIGN.md
-        # §9.14).  No effect with elide_outside off.  MLI_ELIDE_OUTSIDE_SAMPLING=0: the dense sampler
-        self.elide_outside_sampling = os.environ.get("MLI_ELIDE_OUTSIDE_SAMPLING", "1") != "0"
+        for name, env, default, kind in SWITCHES:
+            v = os.environ.get(env)
+            setattr(self, name, default if v is None else int(v) if kind is int else v != "0")
         # stage-b training: the output layers' dW from per-tile partials the heads forward forms
         # while X3 is in registers (mli_rgb_fwd PQ mode + mli_dw4) instead of X3 through HBM and
         # the THIN split-K GEMM; needs N % 32 == 0 (a 32-sample tile within one ray)
@@ -259,32 +302,6 @@ class RenderEngine:
         n = int(np.prod(shape))
         return flat[off:off + n].reshape(shape)
 
-    # ------------------------------------------------------------------ buffers
-    def use_lane(self, lane, geometry_only=False):
-        """Switch to scratch-buffer set ``lane``: renders in flight on different streams (the
-        pipelined inference chunks, Model.inference) each own a buffer set; a lane is reused
-        only on its own stream, so stream order protects it.  ``geometry_only`` (the training
-        prefetch lanes, Trainer.prefetch): the lane owns only the geometry buffers and shares the
-        rest with the other such lanes (_GeometryLane)."""
-        if lane not in self._lanes:
-            if geometry_only:
-                if self._shared_step is None:
-                    self._shared_step = {}
-                self._lanes[lane] = _GeometryLane(self._shared_step)
-            else:
-                self._lanes[lane] = {}
-        self._bufs = self._lanes[lane]
-        if geometry_only != isinstance(self._bufs, _GeometryLane):
-            raise RuntimeError("engine lane %r was created with geometry_only=%s" % (lane, not geometry_only))
-
-    def _buf(self, name, shape, dtype=torch.float32):
-        t = self._bufs.get(name)
-        n = int(np.prod(shape))
-        if t is None or t.numel() < n or t.dtype != dtype:
-            t = torch.empty(n, dtype=dtype, device=self.device)
-            self._bufs[name] = t
-        return t[:n].view(*shape)
-
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
     def rays(self, pose, intr, pose_light, ray_idx, W, R=None, first_pixel=0):
@@ -322,45 +339,46 @@ class RenderEngine:
 
     @torch.no_grad()
     def inside_rays(self, rays, training, elide=True):
-        """The inside-ray list of a pass whose sampler and FIELD pass both skip the rays outside
-        the bounds, built before sample(): one mli_inside_list call that also writes those rays'
-        FIELD rows and their dists.  None where that does not apply (elides(), the two switches):
-        sample() and field() then run as without it."""
+        """The inside-ray list of a pass that skips the rays outside the bounds, built before
+        sample(): one mli_inside_list call that also writes those rays' FIELD rows.  Returns
+        (list, count, sampling): field() evaluates the listed rays only, and with ``sampling``
+        (elide_outside_sampling) so does sample() -- the call then writes the other rays' dists
+        too.  None (a dense pass) where ``elide`` (the pass's heads will elide), elide_outside and
+        elides() do not all hold: the one place that decides this."""
         N = self.cfg.n_samples
-        if not (elide and self.elide_outside and self.elide_outside_sampling and self.elides(N, training)):
+        if not (elide and self.elide_outside and self.elides(N, training)):
             return None
-        R = rays["center"].shape[0]
-        inside = (self._buf("inside_list", (R,), torch.int32), self._buf("n_inside", (1,), torch.int32))
+        R, sampling = rays["center"].shape[0], bool(self.elide_outside_sampling)
+        lst, n = self._buf("inside_list", (R,), torch.int32), self._buf("n_inside", (1,), torch.int32)
         hess = self._buf("hess", (N, R, 3)) if training else None
+        sdf, grad = self._buf("sdf", (N, R)), self._buf("grad", (N, R, 3))
+        fill = (rays["near"], rays["far"], self._buf("dists", (N, R))) if sampling else ()
         # (the heads pad their last workgroup with up to 256 / N - 1 dead rays, processed like
         # live ones: the outside rays that can be such pads are sampled and evaluated too)
         L.call("mli_inside_list", L.InsideListArgs(
-            R, N, 256 // N - 1, L.ptr(rays["outside"]), L.ptr(inside[0]), L.ptr(inside[1]), self.cfg.outside_val,
-            L.ptr(self._buf("sdf", (N, R))), L.ptr(self._buf("grad", (N, R, 3))), L.ptr(hess),
-            L.ptr(rays["near"]), L.ptr(rays["far"]), L.ptr(self._buf("dists", (N, R)))))
-        return inside
+            R, N, 256 // N - 1, L.ptr(rays["outside"]), L.ptr(lst), L.ptr(n), self.cfg.outside_val, L.ptr(sdf),
+            L.ptr(grad), L.ptr(hess), *[L.ptr(t) for t in fill]))
+        return lst, n, sampling
 
     @torch.no_grad()
     def sample(self, rays, u=None, inside=None):
-        """sample_dists_all (neuralangelo/model.py:449-465) -> dists [N][R].  ``inside`` (the
-        lists of inside_rays()): the sdf and fine rounds run for the listed rays only; the
-        intermediate buffers of the other rays are neither written nor read, and their dists are
-        the rows inside_rays() wrote."""
+        """sample_dists_all (neuralangelo/model.py:449-465) -> dists [N][R].  ``inside`` (what
+        inside_rays() returned, with its ``sampling`` set): the sdf and fine rounds run for the
+        listed rays only; the intermediate buffers of the other rays are neither written nor
+        read, and their dists are the rows inside_rays() wrote."""
         cfg = self.cfg
         R = rays["center"].shape[0]
-        Nc, Nf, H = cfg.n_coarse, cfg.n_fine, cfg.n_hier
-        N = cfg.n_samples
-        lst = (None, None) if inside is None else (L.ptr(inside[0]), L.ptr(inside[1]))
-        mode = 0 if inside is None else 2
+        Nc, Nf, H, N = cfg.n_coarse, cfg.n_fine, cfg.n_hier, cfg.n_samples
+        inside = inside[:2] if inside is not None and inside[2] else (None, None)
+        lst = (L.ptr(inside[0]), L.ptr(inside[1]))
+        mode = 0 if inside[0] is None else 2
         d0 = self._buf("d_coarse", (Nc, R))
         uu = None if u is None else u.reshape(R, Nc).contiguous()
         L.call("mli_sample_coarse", L.SampleCoarseArgs(L.ptr(rays["near"]), L.ptr(rays["far"]), L.ptr(uu),
                                                        R, Nc, L.ptr(d0)))
         s0 = self._buf("s_coarse", (Nc, R))
-        self._sdf(rays, d0, Nc, s0, mode=mode, inside=inside or (None, None))
-        da, sa, na = d0, s0, Nc
-        db = sb = None
-        nb = 0
+        self._sdf(rays, d0, Nc, s0, mode=mode, inside=inside)
+        da, sa, na, db, sb, nb = d0, s0, Nc, None, None, 0
         for h in range(H):
             dm = self._buf("d_m%d" % (h & 1), (na + nb, R))
             sm = self._buf("s_m%d" % (h & 1), (na + nb, R))
@@ -371,7 +389,7 @@ class RenderEngine:
             sf = None
             if h < H - 1:
                 sf = self._buf("s_f%d" % (h & 1), (Nf, R))
-                self._sdf(rays, f, Nf, sf, mode=mode, inside=inside or (None, None))
+                self._sdf(rays, f, Nf, sf, mode=mode, inside=inside)
             if self.trace is not None:
                 self.trace.append(dict(merged=dm.clone(), merged_sdf=sm.clone(), fine=f.clone(),
                                        fine_sdf=None if sf is None else sf.clone()))
@@ -382,34 +400,31 @@ class RenderEngine:
         return dists
 
     @torch.no_grad()
-    def field(self, rays, dists, training, elide_outside=False, inside=None, u=None):
-        """The FIELD pass.  ``elide_outside`` (the geometry of a step whose heads will elide, see
-        elides(); a no-op elsewhere): only the rays inside the bounds are evaluated.  The rays
-        outside them get sdf = outside_val and zero gradients / hessians, and their h0 / enc tiles
-        are not written -- such a state is marked ``elided`` and keeps its lane, and densify()
-        turns it into the dense one.  ``inside``: the lists of inside_rays(), which sample() ran
-        on too (the pass is then elided whatever ``elide_outside`` says, and the state keeps the
-        stratified uniforms ``u`` for densify() to re-run the dense sampler)."""
+    def field(self, rays, dists, training, inside=None, u=None):
+        """The FIELD pass.  ``inside`` (what inside_rays() returned): only the listed rays are
+        evaluated.  The rays outside the bounds keep the rows inside_rays() wrote (sdf =
+        outside_val, zero gradients / hessians), and their h0 / enc tiles are not written -- such
+        a state is marked ``elided`` and keeps its lane, and densify() turns it into the dense
+        one.  Where sample() ran on the list too (``sampling_elided``) the state keeps the
+        stratified uniforms ``u`` for densify() to re-run the dense sampler."""
         N, R = dists.shape
-        S = N * R
-        sdf = self._buf("sdf", (N, R))
-        grad = self._buf("grad", (N, R, 3))
+        sdf, grad = self._buf("sdf", (N, R)), self._buf("grad", (N, R, 3))
         hess = self._buf("hess", (N, R, 3)) if training else None
-        h0 = self._buf("h0", (S * 256,), torch.float16)
-        elided = inside is not None or bool(elide_outside and self.elide_outside and self.elides(N, training))
-        sampled = inside is not None
-        if not elided:
-            inside = (None, None)
-        elif not sampled:
-            inside = (self._buf("inside_list", (R,), torch.int32), self._buf("n_inside", (1,), torch.int32))
-            # (the heads pad their last workgroup with up to 256 / N - 1 dead rays, processed like
-            # live ones: the outside rays that can be such pads are evaluated too)
-            L.call("mli_inside_list", L.InsideListArgs(R, N, 256 // N - 1, L.ptr(rays["outside"]), L.ptr(inside[0]),
-                                                       L.ptr(inside[1]), self.cfg.outside_val, L.ptr(sdf),
-                                                       L.ptr(grad), L.ptr(hess)))
-        enc = self._sdf(rays, dists, N, sdf, mode=1, grad=grad, hess=hess, h0=h0, inside=inside)
+        h0 = self._buf("h0", (N * R * 256,), torch.float16)
+        elided = inside is not None
+        sampled = elided and inside[2]
+        enc = self._sdf(rays, dists, N, sdf, mode=1, grad=grad, hess=hess, h0=h0,
+                        inside=inside[:2] if elided else (None, None))
         return dict(sdf=sdf, grad=grad, hess=hess, h0=h0, enc=enc, elided=elided,
-                    lane=self._bufs if elided else None, sampling_elided=sampled, u=u if sampled else None)
+                    lane=self._lane if elided else None, sampling_elided=sampled, u=u if sampled else None)
+
+    def geometry(self, data, W, training, u=None, elide=False):
+        """rays -> inside list -> sampling rounds -> FIELD pass on the current lane and stream: the
+        (rays, dists, fld) of a render state.  ``elide``: this pass's heads will (see inside_rays)."""
+        rays = self.rays(data["pose"], data["intr"], data["pose_light"], data["ray_idx"], W)
+        inside = self.inside_rays(rays, training, elide)
+        dists = self.sample(rays, u, inside)
+        return rays, dists, self.field(rays, dists, training, inside, u)
 
     @torch.no_grad()
     def densify(self, st):
@@ -423,9 +438,7 @@ class RenderEngine:
         rays, dists, fld = st[0], st[1], st[2]
         if not fld.get("elided"):
             return st
-        prev = self._bufs
-        self._bufs = fld["lane"]
-        try:
+        with self.lane(fld["lane"]):
             dense = dict(dists=dists)
             if fld.get("sampling_elided"):
                 u = fld["u"]
@@ -433,8 +446,6 @@ class RenderEngine:
                     u.record_stream(torch.cuda.current_stream(u.device))
                 dense["dists"] = self.sample(rays, u)
             dense.update(self.field(rays, dists, fld["hess"] is not None))
-        finally:
-            self._bufs = prev
         for k in ("dists", "sdf", "grad", "hess", "h0", "enc"):
             have = dists if k == "dists" else fld[k]
             if (dense[k] is None) != (have is None) or (dense[k] is not None
@@ -452,11 +463,9 @@ class RenderEngine:
         """The composite weights alone (mli_composite_fwd with y = NULL): the PQ heads forward
         needs them before the heads run (compute_neus_alphas + alpha_compositing_weights,
         neuralangelo/model.py:492-515, render.py:87-99)."""
-        N, R = dists.shape
-        w = self._buf("weights", (N, R))
-        out = dict(weights=w, rgb=None, o_r=None, o_s=None, o_re=None)
+        out = self._composite_out(dists, outputs=False)
         L.call("mli_composite_fwd", self._composite_args(rays, dists, fld, dict(y=None), s_var, progress, out))
-        return w
+        return out["weights"]
 
     @torch.no_grad()
     def elides(self, N, training):
@@ -487,50 +496,24 @@ class RenderEngine:
         # the x0 image: SDF feature (k-steps 0..15 of each 32-sample tile) + in training the extras
         # (16..18); the WIDE dW operand (ABI 15)
         feat = self._buf("feat", (S * layout.K0,), torch.float16)
-        xT = masks = w = q4 = None
+        xT = masks = w = tl = tr = nl = wl = wr = None
         pq = s_var is not None and self.pq_mode(N, training)
         if training and self.stage == "b" and not self.deterministic:
             # the split-K dW accumulators of this lane's backward: left zero by the last
             # mli_grad_assemble (zero_dw, ABI 17), else zeroed here at the start of the step, where
             # the GPU is not shared with the prefetched geometry (before the heads backward the
             # fill competed with the sampling rounds: 5 -> 19 us)
-            self._zero_once(self._buf("dw", (self._dw_total(),)))
+            self._zero_once(self._buf("dw", (_dw_numel(self._dw_sizes()),)))
         if training:
             xT = self._buf("xT", (nh, 3 if pq else 4, S * 256), torch.float16)  # ACC frag images
             masks = self._buf("masks", (nh, 4, S // 32, 64, 4), torch.int32)
-        tl = tr = nl = wl = wr = None
-        elide = bool(pq and elide and self.elides(N, training))
-        if not elide:
+        if pq and elide and self.elides(N, training):
+            w, tl, tr, nl, wl, wr = self._live_lists(rays, dists, fld, y, s_var, progress)
+        else:
             self.densify((rays, dists, fld))  # every ray's h0 tiles are read
-        if elide:
-            # the live rays of this batch, from the weights (device side: the grids stay S / 256
-            # and the workgroups past the live tiles return at once)
-            tl = self._buf("tile_list", (S // 32,), torch.int32)
-            tr = self._buf("tile_rank", (S // 32 + 1,), torch.int32)
-            nl = self._buf("n_live_tiles", (1,), torch.int32)
-            flags = self._buf("live_flags", (R,), torch.int32)
-        if elide and self.live_tiles_pass:
-            # the weights, the live rays and the nonzero tiles in one pass
-            w = self._buf("weights", (N, R))
-            out = dict(weights=w, rgb=None, o_r=None, o_s=None, o_re=None)
-            wl = self._buf("wtile_list", (S // 32,), torch.int32)
-            wr = self._buf("wtile_rank", (S // 32 + 1,), torch.int32)
-            ticket = self._bufs.get("live_ticket")
-            if ticket is None:   # zeroed once: the pass leaves it zero
-                ticket = self._bufs["live_ticket"] = torch.zeros(1, dtype=torch.int32, device=self.device)
-            L.call("mli_live_tiles", L.LiveTilesArgs(
-                self._composite_args(rays, dists, fld, dict(y=None), s_var, progress, out), L.ptr(y), L.ptr(flags),
-                L.ptr(tl), L.ptr(tr), L.ptr(nl), L.ptr(wl), L.ptr(wr), L.ptr(ticket),
-                0 if self.live_tiles_pass == 2 else 1))
-            if not self.skip_zero_tiles:
-                wl = wr = None
-        elif pq:
-            w = self.weights(rays, dists, fld, s_var, progress)
-            if elide:
-                L.call("mli_live_rays", L.LiveRaysArgs(R, N, L.ptr(w), L.ptr(y), L.ptr(flags),
-                                                       L.ptr(tl), L.ptr(tr), L.ptr(nl)))
-        if pq:
-            q4 = self._buf("q4", (S // 256, layout.q4_segs(N), nh, 257, 4))
+            if pq:
+                w = self.weights(rays, dists, fld, s_var, progress)
+        q4 = self._buf("q4", (S // 256, layout.q4_segs(N), nh, 257, 4)) if pq else None
         L.call("mli_rgb_fwd", L.RgbFwdArgs(R, N, L.ptr(rays["center"]), L.ptr(rays["ray_unit"]),
                                            L.ptr(rays["pts_light"]), L.ptr(dists), L.ptr(fld["grad"]),
                                            L.ptr(fld["h0"]), L.ptr(self.wfwd), L.ptr(y), L.ptr(feat),
@@ -538,18 +521,48 @@ class RenderEngine:
         return dict(y=y, x0T=feat if training else None, xT=xT, masks=masks, feat=feat, q4=q4,
                     tile_list=tl, tile_rank=tr, n_live_tiles=nl, wtile_list=wl, wtile_rank=wr)
 
+    def _live_lists(self, rays, dists, fld, y, s_var, progress):
+        """The composite weights and the live lists of heads(elide=True), the way live_tiles_pass
+        says -> (weights, tile_list, tile_rank, n_live_tiles, wtile_list, wtile_rank).  (Device
+        side: the grids stay S / 256 and the workgroups past the live tiles return at once.)"""
+        N, R = dists.shape
+        T = N * R // 32
+        tl = self._buf("tile_list", (T,), torch.int32)
+        tr = self._buf("tile_rank", (T + 1,), torch.int32)
+        nl = self._buf("n_live_tiles", (1,), torch.int32)
+        flags = self._buf("live_flags", (R,), torch.int32)
+        if not self.live_tiles_pass:   # the weights, then the live rays from them
+            w = self.weights(rays, dists, fld, s_var, progress)
+            L.call("mli_live_rays", L.LiveRaysArgs(R, N, L.ptr(w), L.ptr(y), L.ptr(flags), L.ptr(tl), L.ptr(tr),
+                                                   L.ptr(nl)))
+            return w, tl, tr, nl, None, None
+        # the weights, the live rays and the nonzero tiles in one pass
+        out = self._composite_out(dists, outputs=False)
+        w, comp = out["weights"], self._composite_args(rays, dists, fld, dict(y=None), s_var, progress, out)
+        wl = self._buf("wtile_list", (T,), torch.int32)
+        wr = self._buf("wtile_rank", (T + 1,), torch.int32)
+        step = self._lane.step
+        if "live_ticket" not in step:   # zeroed once: the pass leaves it zero
+            step["live_ticket"] = torch.zeros(1, dtype=torch.int32, device=self.device)
+        L.call("mli_live_tiles", L.LiveTilesArgs(comp, L.ptr(y), L.ptr(flags), L.ptr(tl), L.ptr(tr), L.ptr(nl),
+                                                 L.ptr(wl), L.ptr(wr), L.ptr(step["live_ticket"]),
+                                                 0 if self.live_tiles_pass == 2 else 1))
+        return (w, tl, tr, nl, wl, wr) if self.skip_zero_tiles else (w, tl, tr, nl, None, None)
+
+    def _composite_out(self, dists, outputs=True, extras=False):
+        """The composite kernels' outputs: the weights buffer, fresh rgb ... (``extras``: + inference maps)."""
+        N, R = dists.shape
+        new = lambda c: torch.empty(R, c, device=self.device) if outputs else None  # noqa: E731
+        out = dict(weights=self._buf("weights", (N, R)), rgb=new(3), o_r=new(3), o_s=new(1), o_re=new(3))
+        if extras:
+            out.update(opacity=new(1), gradient=new(3), depth=new(1))
+            if self.cfg.light_visibility:
+                out["blend_dist"] = new(1)
+        return out
+
     @torch.no_grad()
     def composite(self, rays, dists, fld, hd, s_var, progress, training):
-        N, R = dists.shape
-        out = dict(weights=self._buf("weights", (N, R)),
-                   rgb=torch.empty(R, 3, device=self.device), o_r=torch.empty(R, 3, device=self.device),
-                   o_s=torch.empty(R, 1, device=self.device), o_re=torch.empty(R, 3, device=self.device))
-        if not training:
-            out.update(opacity=torch.empty(R, 1, device=self.device),
-                       gradient=torch.empty(R, 3, device=self.device),
-                       depth=torch.empty(R, 1, device=self.device))
-            if self.cfg.light_visibility:
-                out["blend_dist"] = torch.empty(R, 1, device=self.device)
+        out = self._composite_out(dists, extras=not training)
         L.call("mli_composite_fwd", self._composite_args(rays, dists, fld, hd, s_var, progress, out))
         return out
 
@@ -575,9 +588,7 @@ class RenderEngine:
         losses[8] output (its rgb / o_r / o_s / o_re / d_* fields are not read).  Returns the
         composite dict and dz4 for backward()."""
         N, R = dists.shape
-        out = dict(weights=self._buf("weights", (N, R)),
-                   rgb=torch.empty(R, 3, device=self.device), o_r=torch.empty(R, 3, device=self.device),
-                   o_s=torch.empty(R, 1, device=self.device), o_re=torch.empty(R, 3, device=self.device))
+        out = self._composite_out(dists)
         dz4 = self._buf("dz4", (N, R, 8))
         dray = self._buf("dray", (R, 8)) if hd.get("q4") is not None else None
         args = L.CompositeLossArgs(self._composite_args(rays, dists, fld, hd, s_var, progress, out), loss,
@@ -586,21 +597,21 @@ class RenderEngine:
         args.loss.scratch = L.ptr(self._buf("cl_scratch", (n,)))
         L.call("mli_composite_loss", args)
         if defer:  # the loss values: finish_losses(), once the gradients are issued
-            if self._bufs.get("cl_deferred") is not None:
+            if self._lane.step.get("cl_deferred") is not None:
                 raise RuntimeError("composite_loss(defer=True): the previous deferred loss values on this "
                                    "lane were never finished (finish_losses)")
-            self._bufs["cl_deferred"] = args
+            self._lane.step["cl_deferred"] = args
         return out, dz4
 
     def finish_losses(self):
         """The loss values of a deferred composite_loss on this lane (mli_composite_loss_finalize)."""
-        args = self._bufs.pop("cl_deferred", None)
+        args = self._lane.step.pop("cl_deferred", None)
         if args is not None:
             L.call("mli_composite_loss_finalize", args)
 
     def drop_deferred(self):
         """Forget a deferred composite_loss whose step failed (its loss slot is not valid)."""
-        self._bufs.pop("cl_deferred", None)
+        self._lane.step.pop("cl_deferred", None)
 
     @torch.no_grad()
     def light_visibility(self, rays, comp, iters=20):
@@ -635,27 +646,23 @@ class RenderEngine:
     def stamp(self):
         """Identifies the current lane's last render: the render state handed out aliases the
         lane's scratch buffers, so a later render on the same lane overwrites it."""
-        return (id(self._bufs), self._bufs.get("__gen", 0))
+        return (id(self._lane), self._lane.step.get("__gen", 0))
 
     def check_stamp(self, stamp):
-        for bufs in self._lanes.values():
-            if id(bufs) == stamp[0]:
-                if bufs.get("__gen", 0) != stamp[1]:
-                    raise RuntimeError("render state overwritten: another render ran on the same engine lane "
-                                       "between this forward and its backward")
-                return
-        raise RuntimeError("render state of an unknown engine lane")
+        lane = next((ln for ln in self._lanes.values() if id(ln) == stamp[0]), None)
+        if lane is None:
+            raise RuntimeError("render state of an unknown engine lane")
+        if lane.step.get("__gen", 0) != stamp[1]:
+            raise RuntimeError("render state overwritten: another render ran on the same engine lane "
+                               "between this forward and its backward")
 
     def render(self, data, s_var, progress, training, u=None, W=512, composite=True, elide=False):
-        """rays -> sampling -> FIELD -> heads -> composite; ``composite=False`` stops after the
+        """geometry() -> heads -> composite; ``composite=False`` stops after the
         heads (comp None: the fused training tail, composite_loss, composites); ``elide``: as
         heads()."""
-        self._bufs["__gen"] = self._bufs.get("__gen", 0) + 1
-        rays = self.rays(data["pose"], data["intr"], data["pose_light"], data["ray_idx"], W)
-        elide_outside = elide and s_var is not None
-        inside = self.inside_rays(rays, training, elide_outside)
-        dists = self.sample(rays, u, inside=inside)
-        fld = self.field(rays, dists, training, elide_outside=elide_outside, inside=inside, u=u)
+        step = self._lane.step
+        step["__gen"] = step.get("__gen", 0) + 1
+        rays, dists, fld = self.geometry(data, W, training, u, elide and s_var is not None)
         hd = self.heads(rays, dists, fld, training, s_var, progress, elide=elide)
         if not composite:
             return rays, dists, fld, hd, None
@@ -667,13 +674,7 @@ class RenderEngine:
     # ------------------------------------------------------------------ backward
     @staticmethod
     def _dw_sizes():
-        sizes = []
-        for name, k_in, k_out in layout.HEADS:
-            sizes += [(256, layout.K0), (256, 256), (256, 256), (256, 256), (k_out, 256)]
-        return sizes
-
-    def _dw_total(self):
-        return sum(m * k + m for m, k in self._dw_sizes())
+        return [mk for _, _, k_out in layout.HEADS for mk in _head_dw_sizes(k_out)]
 
     def _wgrad_plan(self, dzT, dz4T, hd, dwbuf, flat, grad_out, S, rebuild=None):
         """Split-K jobs (host array) + device assemble descriptors + (PQ mode) the mli_dw4
@@ -783,7 +784,7 @@ class RenderEngine:
                                                            scale, L.ptr(dz4),
                                                            L.ptr(self._buf("dray", (R, 8)) if pq else None)))
         dz4T = None if pq else self._buf("dz4T", (3, S * 16), torch.float16)  # one-k-step frag images
-        dwbuf = self._buf("dw", (self._dw_total(),))
+        dwbuf = self._buf("dw", (_dw_numel(self._dw_sizes()),))
         zero_dw = 0 if self.deterministic else 1
         if zero_dw:
             self._zero_once(dwbuf)   # split-K partials add into it (fp32 atomics)
@@ -834,12 +835,11 @@ class RenderEngine:
 
     def _dw4(self, R, N, hd, scale, dw4, db4, k4):
         """PQ mode: the output layers' dW / db from the forward's q4 and the per-ray D."""
-        args = L.Dw4Args(R, N, 3, L.ptr(hd["q4"]), L.ptr(self._bufs["dray"]), scale / L.Q4_SCALE,
+        args = L.Dw4Args(R, N, 3, L.ptr(hd["q4"]), L.ptr(self._lane.step["dray"]), scale / L.Q4_SCALE,
                          (C.c_void_p * 3)(*dw4), (C.c_void_p * 3)(*db4), (C.c_int * 3)(*k4), None,
                          L.ptr(hd.get("tile_rank")))
         args.workspace = L.ptr(self._buf("dw4_ws", (L.workspace("mli_dw4", args)[0] // 4,)))
         L.call("mli_dw4", args)
-
 
     # ------------------------------------------------------------------ stage a backward
     def _assemble_desc(self, dw, db, v, g, n_out, k_ref, k_pack, kinv, gv, gg, gb, plain=0):
@@ -853,7 +853,7 @@ class RenderEngine:
         if getattr(self, "_aplan", None) is not None and self._aplan[0] == key:
             return self._aplan[1:]
         head = layout.HEADS_A[0][0]
-        sizes = [(256, layout.K0), (256, 256), (256, 256), (256, 256), (3, 256)]
+        sizes = _head_dw_sizes(3)
         dw, off = bufs["dw"], 0
         jobs_s, jobs_5s, descs, keep = [], [], [], []
 
@@ -921,7 +921,7 @@ class RenderEngine:
         outside that mode), else the fp32 table gradient itself."""
         if self.deterministic:
             return self._buf("hash_ws", (grad_table.numel(),), torch.int64)
-        self._bufs.pop("hash_ws", None)
+        self._lane.step.pop("hash_ws", None)
         return grad_table
 
     @torch.no_grad()
@@ -975,9 +975,8 @@ class RenderEngine:
         L.call("mli_hash_bwd", L.HashBwdArgs(R, N, L.ptr(rays["center"]), L.ptr(rays["ray_unit"]), L.ptr(dists),
                                              L.ptr(d_enc), self.levels, self.eps, int(self.active_levels),
                                              L.ptr(grad_table), det, L.ptr(hws), grad_table.numel()))
-        dw_total = sum(m * k + m for m, k in [(256, layout.K0), (256, 256), (256, 256), (256, 256), (3, 256),
-                                              (256, 256), (256, layout.SDF_K0)])
-        b["dw"] = self._buf("dw_a", (dw_total,))
+        # the head's layers, neural_sdf.mlp.linears.1 and .0 (_plan_a)
+        b["dw"] = self._buf("dw_a", (_dw_numel(_head_dw_sizes(3) + [(256, 256), (256, layout.SDF_K0)]),))
         js, j5, ad, n_desc, _, _ = self._plan_a(b, flat, grad_flat, S)
         zero_dw = 0 if self.deterministic else 1
         if zero_dw:   # left zero by the last assemble (ABI 17), else one fill

@@ -28,7 +28,7 @@ import torch
 import torch.nn.functional as F
 
 from . import layout
-from .engine import PathConfig, RenderEngine
+from .engine import SWITCHES, PathConfig, RenderEngine
 from .hashgrid import GRID_DEFAULTS, level_table
 
 
@@ -254,12 +254,8 @@ class Model(torch.nn.Module):
         self.image_width = self.image_size_train[1]
         self.deterministic = False  # fixed-order gradient reductions (RenderEngine.deterministic)
         self.pq = True              # stage-b output-layer dW from the forward's partials (RenderEngine.pq)
-        self.dz3_rebuild = None     # True / False: override RenderEngine.dz3_rebuild (None: its default)
-        self.elide_dead_rays = None  # True / False: override RenderEngine.elide_dead_rays (None: its default)
-        self.skip_zero_tiles = None  # True / False: override RenderEngine.skip_zero_tiles (None: its default)
-        self.elide_outside = None    # True / False: override RenderEngine.elide_outside (None: its default)
-        # True / False: override RenderEngine.elide_outside_sampling (None: its default)
-        self.elide_outside_sampling = None
+        for name, _, _, _ in SWITCHES:   # a value other than None overrides the engine's (prepare)
+            setattr(self, name, None)
 
     # -------------------------------------------------------------- parameter plumbing
     def _view(self, name, flat=None):
@@ -385,16 +381,9 @@ class Model(torch.nn.Module):
         eng = self.engine
         eng.deterministic = self.deterministic
         eng.pq = self.pq
-        if self.dz3_rebuild is not None:
-            eng.dz3_rebuild = self.dz3_rebuild
-        if self.elide_dead_rays is not None:
-            eng.elide_dead_rays = self.elide_dead_rays
-        if self.skip_zero_tiles is not None:
-            eng.skip_zero_tiles = self.skip_zero_tiles
-        if self.elide_outside is not None:
-            eng.elide_outside = self.elide_outside
-        if self.elide_outside_sampling is not None:
-            eng.elide_outside_sampling = self.elide_outside_sampling
+        for name, _, _, _ in SWITCHES:
+            if getattr(self, name) is not None:
+                setattr(eng, name, getattr(self, name))
         eng.set_normal_eps(sdf.normal_eps)
         eng.active_levels = int(sdf.active_levels)
         l0 = sdf.mlp.linears[0]
@@ -515,14 +504,12 @@ class Model(torch.nn.Module):
                 R = min(self.rand_rays_val, hi - start)
                 Rp = -(-R // step) * step
                 lane = i % 2 if self.pipeline_chunks else 0
-                with torch.cuda.stream(self._streams[lane]):
-                    self.engine.use_lane(lane)
+                with torch.cuda.stream(self._streams[lane]), self.engine.lane(lane):
                     ridx = torch.arange(start, start + Rp, device=dev).clamp_(max=start + R - 1)[None]
                     d = dict(pose=data["pose"], intr=data["intr"], pose_light=data["pose_light"], ray_idx=ridx)
                     st = self.engine.render(d, self.s_var.detach(), self.progress, False, u=None, W=W)
                     parts.append(sh.pack(st[4], vis)[:R])
         finally:
-            self.engine.use_lane(0)
             for s in self._streams:
                 main.wait_stream(s)
         for p in parts:

@@ -513,7 +513,7 @@ class Trainer:
         Memory: a prefetch lane holds only the geometry of its batch (rays, the sampling rounds,
         the FIELD pass: sdf / grad / hess, the h0 and encoding images); the step's buffers
         (activations, dZ images, masks, dW slabs) are one set shared by the lanes
-        (engine._GeometryLane), since the steps themselves run one after another on the main
+        (engine._Lane), since the steps themselves run one after another on the main
         stream.  bench.py reports the allocator's peak as ``hbm_peak_gib``."""
         d = int(d)
         if d < 1:
@@ -734,25 +734,14 @@ class Trainer:
         side.wait_event(ready)
         lane = ("pf", self._pf_lane)
         self._pf_lane = (self._pf_lane + 1) % (self.prefetch_depth + 1)
-        prev = eng._bufs
-        try:
-            with torch.cuda.stream(side):
-                for k in ("ray_idx", "pose", "intr", "pose_light"):
-                    data[k].record_stream(side)
-                eng.use_lane(lane, geometry_only=True)
-                rays = eng.rays(data["pose"], data["intr"], data["pose_light"], data["ray_idx"],
-                                m.image_size_train[1])
-                uu = m.stratified_uniforms(data, u)
-                # one inside-ray list for the sampling rounds and the FIELD pass
-                # (a step that turns out not to elide densifies the state: RenderEngine.heads)
-                inside = eng.inside_rays(rays, True, self.fused_tail)
-                dists = eng.sample(rays, uu, inside=inside)
-                fld = eng.field(rays, dists, True, elide_outside=self.fused_tail, inside=inside, u=uu)
-        finally:
-            eng._bufs = prev
+        with torch.cuda.stream(side), eng.lane(lane, geometry_only=True):
+            for k in ("ray_idx", "pose", "intr", "pose_light"):
+                data[k].record_stream(side)
+            # (a step that turns out not to elide densifies the state: RenderEngine.heads)
+            geo = eng.geometry(data, m.image_size_train[1], True, m.stratified_uniforms(data, u), self.fused_tail)
         done = torch.cuda.Event()
         done.record(side)
-        self._pending.append((data, lane, rays, dists, fld, done))
+        self._pending.append((data, lane) + geo + (done,))
 
     def _take_prefetched(self, data):
         for i, pf in enumerate(self._pending):
@@ -786,14 +775,12 @@ class Trainer:
             return self.train_step_a(data, u, return_outputs)
         if not set(self.weights) <= FUSED_LOSSES:
             return self._train_step_autograd(data, u)
-        m = self.model
+        self.model.prepare()   # (on the lane current here, not a prefetch lane)
         pf = self._take_prefetched(data)
-        prev = m.engine._bufs if m.engine is not None else None
-        try:
+        if pf is None:
+            return self._train_step_b(data, u, return_outputs, None)
+        with self.model.engine.lane(pf[0], geometry_only=True):   # the lane that holds its geometry
             return self._train_step_b(data, u, return_outputs, pf)
-        finally:
-            if prev is not None:
-                m.engine._bufs = prev
 
     def _grad_buffer(self):
         """The flat gradient + N_METRICS metric slots: the loss kernel writes the step's loss
@@ -823,7 +810,6 @@ class Trainer:
 
     def _train_step_b(self, data, u, return_outputs, pf):
         m = self.model
-        m.prepare()
         m.image_width = m.image_size_train[1]
         eng = m.engine
         fused = self.fused_tail
@@ -833,7 +819,6 @@ class Trainer:
         else:
             lane, rays, dists, fld, done = pf
             torch.cuda.current_stream(m.flat.device).wait_event(done)
-            eng.use_lane(lane, geometry_only=True)
             hd = eng.heads(rays, dists, fld, True, m.s_var.detach(), m.progress, elide=fused)
             comp = None if fused else eng.composite(rays, dists, fld, hd, m.s_var.detach(), m.progress, True)
             st = (rays, dists, fld, hd, comp)

@@ -8,19 +8,18 @@ indices and of three trainable parameters.  ``install(monkeypatch)`` swaps it in
 torch versions of the two kernel calls the Trainer issues itself (loss, AdamW).  Nothing here is
 product code; the product path raises without a GPU (RenderEngine.__init__).
 """
-import math
-
 import torch
 
+from mli_nerf_amd.engine import _Lanes
 
-class StubEngine:
+
+class StubEngine(_Lanes):
     def __init__(self, cfg, device, stage="b"):
         self.cfg, self.device, self.stage = cfg, torch.device(device), stage
         self.active_levels = cfg.levels
         self.table16 = None
         self.gate_wgrad, self.gate_event = False, None
-        self._lanes = {0: {}}
-        self._bufs = self._lanes[0]
+        _Lanes.__init__(self)   # use_lane / lane / _buf: the engine's own
         self.flat = None
 
     # parameter plumbing (RenderEngine keeps device weight images; the stub keeps the buffer)
@@ -39,19 +38,8 @@ class StubEngine:
     def pack_heads(self, flat, sdf_l1):
         self.flat = flat
 
-    def use_lane(self, lane):
-        self._bufs = self._lanes.setdefault(lane, {})
-
-    def _buf(self, name, shape, dtype=torch.float32):
-        t = self._bufs.get(name)
-        n = math.prod(shape)
-        if t is None or t.numel() < n or t.dtype != dtype:
-            t = torch.empty(n, dtype=dtype, device=self.device)
-            self._bufs[name] = t
-        return t[:n].view(*shape)
-
     def stamp(self):
-        return (id(self._bufs), self._bufs.get("__gen", 0))
+        return (id(self._lane), self._lane.step.get("__gen", 0))
 
     def check_stamp(self, stamp):
         pass

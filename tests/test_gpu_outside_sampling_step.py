@@ -70,11 +70,9 @@ def _pipeline(arm):
     tr.prefetch_gate, tr.prefetch_depth = "heads", 2
     tr.model.prepare()
     eng = tr.model.engine
-    prev = eng._bufs
     for lane in range(3):
-        eng.use_lane(("pf", lane), geometry_only=True)
-        _poison(eng)
-    eng._bufs = prev
+        with eng.lane(("pf", lane), geometry_only=True):
+            _poison(eng)
     batches = [_batch(_hit(p), NC, seed=i + 1) for i, p in enumerate(("some", "none", "all", "one", "some", "all"))]
     hist = []
     for j in range(2):
