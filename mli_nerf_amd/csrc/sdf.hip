@@ -177,7 +177,12 @@ MLI_FI float sdf_point(const uint8_t* lds, const uint16_t* __restrict__ table, c
 // gathered once per level and every tap that falls in the same grid cell (most of them:
 // the taps are eps = 1/2048/sqrt(3) away, <= 0.14 cells even at the finest level) reuses
 // them with its own trilinear weights; only the other lanes gather.  Same arithmetic as
-// hash_level (bit-identical encodings), written as B-fragment images for phase B.
+// hash_level in source, not in bits: here the compiler folds the last corner's fma and the
+// fp16 conversion into one v_fma_mixlo_f16 (one rounding, straight to fp16), while sdf_kernel
+// rounds the fp32 sum and then converts (v_fma_mix_f32 + v_cvt_f16_f32, two roundings).  About
+// 6 in 1e5 encodings differ by one fp16 ulp, so SDF mode and FIELD's centre agree to ~5e-7
+// in the sdf, not bit for bit (tests/test_gpu_field_values.py).  Written as B-fragment images
+// for phase B.
 constexpr int TAPS = 5;
 
 // The 5 points' encodings at one level pair (lane half h = level 2qq+h), taps' own gathers

@@ -7,7 +7,9 @@ rounded to fp16 up to one fp16 ulp (|e| <= 2^-10 |v| + 2^-24; the oracle sums th
 another order).  At the finest levels most taps leave the center's cell (the job path); the
 coarse levels reuse the center's corners -- both are covered, and the stage-a case masks the
 levels >= active_levels (coarse-to-fine) to zero.  The FIELD outputs built on this image (sdf,
-normals, hessian, h0) are checked against the oracle in tests/test_gpu_parity.py."""
+normals, hessian, h0) are checked in tests/test_gpu_field_values.py, in float64 from this image
+and the packed weights (there also the image at a tap size of 2^-6, where almost every tap leaves
+the center's cell); tests/test_gpu_parity.py compares sdf and normals with the fp32 oracle."""
 import pytest
 import torch
 
