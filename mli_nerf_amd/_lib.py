@@ -312,6 +312,25 @@ MESH_CC_MAX_ROUNDS = 4096  # MLI_CC_MAX_ROUNDS
 MESH_CC_ENTRY_POINTS = {"mli_cc_init": MeshCcArgs, "mli_cc_round": MeshCcArgs, "mli_cc_stats": MeshCcArgs}
 MESH_CC_WORKSPACE = {"mli_cc_init": 4}
 
+# ---------------------------------------------------------------- include/mli_metrics.h
+class MetricsArgs(C.Structure):
+    _fields_ = [("B", I32), ("C", I32), ("H", I32), ("W", I32), ("quantize", I32), ("mask_pred", I32),
+                ("gamma_target", I32), ("inv_gamma", F64), ("pred_f32", P), ("pred_u8", P), ("target_f32", P),
+                ("target_u8", P), ("alpha_f32", P), ("alpha_u8", P), ("mse", P), ("psnr", P), ("ssim", P),
+                ("ssim_channels", P), ("prep_pred", P), ("prep_target", P), ("partial", P)]
+
+
+METRICS_ABI_VERSION = 1      # include/mli_metrics.h MLI_METRICS_ABI_VERSION
+METRICS_MAX_SIDE = 16384     # MLI_METRICS_MAX_SIDE
+METRICS_MAX_IMAGES = 16383   # MLI_METRICS_MAX_IMAGES
+METRICS_MAX_CHANNELS = 4     # MLI_METRICS_MAX_CHANNELS
+METRICS_WINDOW = 7           # MLI_METRICS_WINDOW
+METRICS_TILE = (32, 8)       # MLI_METRICS_TILE_X, MLI_METRICS_TILE_Y
+
+# the image-metric op, versioned apart from the four ABIs above
+METRICS_ENTRY_POINTS = {"mli_image_metrics": MetricsArgs}
+METRICS_WORKSPACE = {"mli_image_metrics": 1}
+
 _lib = None
 
 
@@ -323,12 +342,14 @@ def lib():
                               "there is no CPU fallback for the hot path" % LIB_PATH)
         _lib = C.CDLL(LIB_PATH)
         for name, st in list(ENTRY_POINTS.items()) + list(MESH_ENTRY_POINTS.items()) + list(
-                LABELS_ENTRY_POINTS.items()) + list(MESH_CC_ENTRY_POINTS.items()):
+                LABELS_ENTRY_POINTS.items()) + list(MESH_CC_ENTRY_POINTS.items()) + list(
+                METRICS_ENTRY_POINTS.items()):
             fn = getattr(_lib, name)
             fn.argtypes = [C.POINTER(st), P]
             fn.restype = I32
         for table, points in ((WORKSPACE, ENTRY_POINTS), (MESH_WORKSPACE, MESH_ENTRY_POINTS),
-                              (LABELS_WORKSPACE, LABELS_ENTRY_POINTS), (MESH_CC_WORKSPACE, MESH_CC_ENTRY_POINTS)):
+                              (LABELS_WORKSPACE, LABELS_ENTRY_POINTS), (MESH_CC_WORKSPACE, MESH_CC_ENTRY_POINTS),
+                              (METRICS_WORKSPACE, METRICS_ENTRY_POINTS)):
             for name in table:
                 fn = getattr(_lib, name + "_workspace")
                 fn.argtypes = [C.POINTER(points[name]), C.POINTER(I64)]
@@ -336,13 +357,15 @@ def lib():
         _lib.mli_mesh_abi_version.restype = I32
         _lib.mli_labels_abi_version.restype = I32
         _lib.mli_mesh_cc_abi_version.restype = I32
+        _lib.mli_metrics_abi_version.restype = I32
         _lib.mli_abi_version.restype = I32
         _lib.mli_error_string.restype = C.c_char_p
         _lib.mli_error_string.argtypes = [I32]
         _lib.mli_source_hash.restype = C.c_char_p
         if (_lib.mli_abi_version() != ABI_VERSION or _lib.mli_mesh_abi_version() != MESH_ABI_VERSION
                 or _lib.mli_labels_abi_version() != LABELS_ABI_VERSION
-                or _lib.mli_mesh_cc_abi_version() != MESH_CC_ABI_VERSION):
+                or _lib.mli_mesh_cc_abi_version() != MESH_CC_ABI_VERSION
+                or _lib.mli_metrics_abi_version() != METRICS_ABI_VERSION):
             raise ImportError("libmli_hip.so ABI mismatch")
         from . import build as _build
         # in-tree sources: the in-tree library must match them.  Only a library OUTSIDE the in-tree
@@ -376,7 +399,7 @@ def workspace(name, args):
     if rc != 0:
         raise RuntimeError("%s_workspace failed: %s (%d)" % (name, lib().mli_error_string(rc).decode(), rc))
     return [int(out[i]) for i in range(WORKSPACE.get(name) or MESH_WORKSPACE.get(name) or LABELS_WORKSPACE.get(name)
-                                         or MESH_CC_WORKSPACE[name])]
+                                         or MESH_CC_WORKSPACE.get(name) or METRICS_WORKSPACE[name])]
 
 
 def ptr(t):

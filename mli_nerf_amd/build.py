@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmli_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["rays.hip", "sdf.hip", "mlp_fwd.hip", "mlp_fwd_pq.hip", "mlp_fwd_train.hip", "mlp_bwd.hip", "mlp_geo.hip",
-           "wgrad.hip", "params.hip", "loss.hip", "mesh.hip", "labels.hip", "mesh_cc.hip"]
+           "wgrad.hip", "params.hip", "loss.hip", "mesh.hip", "labels.hip", "mesh_cc.hip", "metrics.hip"]
 # sdf.hip: no SLP packing, so fma(fp16 -> fp32 feature, w, acc) selects v_fma_mix_f32 (one
 # instruction) instead of v_cvt_f32_f16 x2 + v_pk_fma_f32
 # No SLP packing of scalar fp32 math in the MFMA and geometry kernels: v_pk_*_f32 beside MFMAs
@@ -34,7 +34,8 @@ def _deps():
     return [os.path.join(CSRC, s) for s in SOURCES] + sorted(
         os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [
         os.path.join(REPO, "include", "mli_hip.h"), os.path.join(REPO, "include", "mli_mesh.h"),
-        os.path.join(REPO, "include", "mli_labels.h"), os.path.join(REPO, "include", "mli_mesh_cc.h")]
+        os.path.join(REPO, "include", "mli_labels.h"), os.path.join(REPO, "include", "mli_mesh_cc.h"),
+        os.path.join(REPO, "include", "mli_metrics.h")]
 
 
 def source_hash():
