@@ -331,6 +331,31 @@ METRICS_TILE = (32, 8)       # MLI_METRICS_TILE_X, MLI_METRICS_TILE_Y
 METRICS_ENTRY_POINTS = {"mli_image_metrics": MetricsArgs}
 METRICS_WORKSPACE = {"mli_image_metrics": 1}
 
+# ---------------------------------------------------------------- include/mli_relight.h
+class LightPointsArgs(C.Structure):
+    _fields_ = [("L", I32), ("R", I32), ("pose_lights", P), ("pts_light", P)]
+
+
+class CameraHitArgs(C.Structure):
+    _fields_ = [("R", I32), ("center", P), ("ray_unit", P), ("near_", P), ("far_", P), ("blend_dist", P),
+                ("camera_ray_type", I32), ("iters", I32), ("table", P), ("levels", GridLevels),
+                ("active_levels", I32), ("wsdf", P), ("inter_dist", P), ("inter_mask", P), ("inter_pts", P)]
+
+
+class LightShadowsArgs(C.Structure):
+    _fields_ = [("L", I32), ("R", I32), ("pts_light", P), ("inter_pts", P), ("gradient", P), ("vis_box", I32),
+                ("vis_r2", F32), ("aabb", F32 * 6), ("gamma", F32), ("iters", I32), ("table", P),
+                ("levels", GridLevels), ("active_levels", I32), ("wsdf", P), ("visibility", P),
+                ("normal_x_light", P), ("pseudo_shading", P)]
+
+
+RELIGHT_ABI_VERSION = 1      # include/mli_relight.h MLI_RELIGHT_ABI_VERSION
+
+# the multi-light ops, versioned apart from the five ABIs above; none needs scratch
+RELIGHT_ENTRY_POINTS = {"mli_light_points": LightPointsArgs, "mli_camera_hit": CameraHitArgs,
+                        "mli_light_shadows": LightShadowsArgs}
+RELIGHT_WORKSPACE = {}
+
 _lib = None
 
 
@@ -343,7 +368,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         for name, st in list(ENTRY_POINTS.items()) + list(MESH_ENTRY_POINTS.items()) + list(
                 LABELS_ENTRY_POINTS.items()) + list(MESH_CC_ENTRY_POINTS.items()) + list(
-                METRICS_ENTRY_POINTS.items()):
+                METRICS_ENTRY_POINTS.items()) + list(RELIGHT_ENTRY_POINTS.items()):
             fn = getattr(_lib, name)
             fn.argtypes = [C.POINTER(st), P]
             fn.restype = I32
@@ -358,6 +383,7 @@ def lib():
         _lib.mli_labels_abi_version.restype = I32
         _lib.mli_mesh_cc_abi_version.restype = I32
         _lib.mli_metrics_abi_version.restype = I32
+        _lib.mli_relight_abi_version.restype = I32
         _lib.mli_abi_version.restype = I32
         _lib.mli_error_string.restype = C.c_char_p
         _lib.mli_error_string.argtypes = [I32]
@@ -365,7 +391,8 @@ def lib():
         if (_lib.mli_abi_version() != ABI_VERSION or _lib.mli_mesh_abi_version() != MESH_ABI_VERSION
                 or _lib.mli_labels_abi_version() != LABELS_ABI_VERSION
                 or _lib.mli_mesh_cc_abi_version() != MESH_CC_ABI_VERSION
-                or _lib.mli_metrics_abi_version() != METRICS_ABI_VERSION):
+                or _lib.mli_metrics_abi_version() != METRICS_ABI_VERSION
+                or _lib.mli_relight_abi_version() != RELIGHT_ABI_VERSION):
             raise ImportError("libmli_hip.so ABI mismatch")
         from . import build as _build
         # in-tree sources: the in-tree library must match them.  Only a library OUTSIDE the in-tree

@@ -35,7 +35,7 @@ def _deps():
         os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [
         os.path.join(REPO, "include", "mli_hip.h"), os.path.join(REPO, "include", "mli_mesh.h"),
         os.path.join(REPO, "include", "mli_labels.h"), os.path.join(REPO, "include", "mli_mesh_cc.h"),
-        os.path.join(REPO, "include", "mli_metrics.h")]
+        os.path.join(REPO, "include", "mli_metrics.h"), os.path.join(REPO, "include", "mli_relight.h")]
 
 
 def source_hash():

@@ -7,10 +7,18 @@
 // Compiled with -ffp-contract=off: products and sums round like the reference's torch ops.
 #include "common.h"
 #include "loss.h"
+#include "mli_relight.h"
 
 namespace {
 
 // --------------------------------------------------------------------------- rays
+// The light position of a w2l pose Q = [R_l | t_l]: component i of -R_l^T t_l (Pose.invert,
+// camera.py:46-52; NeuralLumen utils.py:61-79) -- one definition for rays_kernel and
+// light_points_kernel, so the two write the same bits.
+MLI_FI float light_pos(const float* Q, int i) {
+  return -((Q[4 * 0 + i] * Q[3] + Q[4 * 1 + i] * Q[7]) + Q[4 * 2 + i] * Q[11]);
+}
+
 __global__ __launch_bounds__(256) void rays_kernel(mli_rays_args a) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.R) return;
@@ -33,8 +41,7 @@ __global__ __launch_bounds__(256) void rays_kernel(mli_rays_args a) {
       for (int j = 0; j < 3; ++j) T[4 * i + j] = P[4 * j + i];
       T[4 * i + 3] = -((P[4 * 0 + i] * P[3] + P[4 * 1 + i] * P[7]) + P[4 * 2 + i] * P[11]);
     }
-    const float* Q = a.pose_light;
-    for (int i = 0; i < 3; ++i) TL[i] = -((Q[4 * 0 + i] * Q[3] + Q[4 * 1 + i] * Q[7]) + Q[4 * 2 + i] * Q[11]);
+    for (int i = 0; i < 3; ++i) TL[i] = light_pos(a.pose_light, i);
   }
   // img2cam: [px, py, 1] @ Kinv^T   (camera.py:259-260)
   float cam[3];
@@ -62,6 +69,15 @@ __global__ __launch_bounds__(256) void rays_kernel(mli_rays_args a) {
   a.near_[r] = nr;
   a.far_[r] = fr;
   a.outside[r] = out ? 1 : 0;
+}
+
+// pts_light of L lights (include/mli_relight.h): element e = (l * R + r) * 3 + i, one thread each
+__global__ __launch_bounds__(256) void light_points_kernel(mli_light_points_args a) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = 3 * (int64_t)a.R;
+  if (e >= row * a.L) return;
+  const int l = (int)(e / row), i = (int)(e % 3);
+  a.pts_light[e] = light_pos(a.pose_lights + 12 * l, i);
 }
 
 // --------------------------------------------------------------------------- sampling
@@ -728,6 +744,15 @@ __global__ __launch_bounds__(256) void ray_batch_kernel(mli_ray_batch_args a) {
 extern "C" int mli_rays(const mli_rays_args* a, mli_stream_t s) {
   if (a->R <= 0) return 0;
   hipLaunchKernelGGL(rays_kernel, dim3((a->R + 255) / 256), dim3(256), 0, (hipStream_t)s, *a);
+  MLI_LAUNCH_CHECK();
+}
+
+extern "C" int mli_light_points(const mli_light_points_args* a, mli_stream_t s) {
+  if (a->L <= 0 || a->R <= 0) return 0;
+  if (!a->pose_lights || !a->pts_light) return (int)hipErrorInvalidValue;
+  if ((int64_t)a->L * a->R > INT32_MAX) return (int)hipErrorInvalidValue;
+  const int64_t n = (int64_t)a->L * a->R * 3;
+  hipLaunchKernelGGL(light_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, *a);
   MLI_LAUNCH_CHECK();
 }
 

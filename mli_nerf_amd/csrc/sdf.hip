@@ -20,6 +20,7 @@
 // B-fragment images, then field_mlp_kernel streams them through layer 0 + softplus + sdf
 // head.  Chunks keep the encodings Infinity-Cache resident between the two.
 #include "hashgrid.h"
+#include "mli_relight.h"
 
 #include <type_traits>
 
@@ -1223,6 +1224,27 @@ struct TraceArgs {
 // halves split the hash levels, as sdf_kernel), `iters` SDF evaluations of the moving point;
 // dist += sdf while the ray is live, a ray dies once dist leaves [near, far]; finally
 // dist = clamp(dist, near, far) (torch.clamp: NaN propagates) and pts = o + v dist.
+// The trace of one ray per lane (both lane halves hold the same ray): `iters` steps from d, then
+// the clamp.  Returns the distance; `live`: the ray never left [nr, fr].  The one definition of
+// trace_kernel (camera and per-light rays) and shadow_pairs_kernel (all lights' rays).
+MLI_FI float trace_ray(const uint8_t* lds, const uint16_t* __restrict__ table, const mli_grid_levels& L, int active,
+                       int iters, int lane, float o0, float o1, float o2, float v0, float v1, float v2, float nr,
+                       float fr, float d, bool& live) {
+  live = true;
+#pragma unroll 1
+  for (int it = 0; it < iters; ++it) {
+    const uint8_t* lds_t = lds + opaque_v(0);
+    const float px = __fadd_rn(o0, __fmul_rn(v0, d));
+    const float py = __fadd_rn(o1, __fmul_rn(v1, d));
+    const float pz = __fadd_rn(o2, __fmul_rn(v2, d));
+    const float s = sdf_point(lds_t, table, L, active, lane, px, py, pz, nullptr);
+    if (live) d = d + s;
+    if (d > fr) live = false;
+    if (d < nr) live = false;
+  }
+  return d < nr ? nr : (d > fr ? fr : d);
+}
+
 __global__ __launch_bounds__(256) void trace_kernel(TraceArgs t) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   load_weights(lds, t.wsdf);
@@ -1236,20 +1258,9 @@ __global__ __launch_bounds__(256) void trace_kernel(TraceArgs t) {
     const float o0 = t.origin[3 * rr], o1 = t.origin[3 * rr + 1], o2 = t.origin[3 * rr + 2];
     const float v0 = t.dir[3 * rr], v1 = t.dir[3 * rr + 1], v2 = t.dir[3 * rr + 2];
     const float nr = t.near_[rr], fr = t.far_[rr];
-    float d = t.start ? t.start[rr] : nr;
-    bool live = true;
-#pragma unroll 1
-    for (int it = 0; it < t.iters; ++it) {
-      const uint8_t* lds_t = lds + opaque_v(0);
-      const float px = __fadd_rn(o0, __fmul_rn(v0, d));
-      const float py = __fadd_rn(o1, __fmul_rn(v1, d));
-      const float pz = __fadd_rn(o2, __fmul_rn(v2, d));
-      const float s = sdf_point(lds_t, t.table, t.levels, t.active, lane, px, py, pz, nullptr);
-      if (live) d = d + s;
-      if (d > fr) live = false;
-      if (d < nr) live = false;
-    }
-    d = d < nr ? nr : (d > fr ? fr : d);
+    bool live;
+    const float d = trace_ray(lds, t.table, t.levels, t.active, t.iters, lane, o0, o1, o2, v0, v1, v2, nr, fr,
+                              t.start ? t.start[rr] : nr, live);
     if (valid && h == 0) {
       t.dist[r] = d;
       t.mask[r] = live ? 1 : 0;
@@ -1273,44 +1284,106 @@ __global__ __launch_bounds__(256) void blend_z_kernel(mli_light_visibility_args 
 }
 
 // light ray from the light position to the camera-ray intersection (model.py:149-173)
+// The light ray of one (light position c, intersection ip) pair: unit direction v, its visibility
+// bounds' near nl, the target distance ft = |ip - c| - 1e-3 and `inside` (the target lies within
+// the bounds).  One definition for light_prep_kernel and shadow_pairs_kernel.
+MLI_FI void light_ray(const float (&c)[3], const float (&ip)[3], int box, float r2, const float* aabb,
+                      float (&v)[3], float& nl, float& ft, bool& inside) {
+  float lr[3];
+  for (int i = 0; i < 3; ++i) lr[i] = ip[i] - c[i];
+  const float n = sqrtf((lr[0] * lr[0] + lr[1] * lr[1]) + lr[2] * lr[2]);
+  const float den = fmaxf(n, 1e-12f);  // F.normalize
+  for (int i = 0; i < 3; ++i) v[i] = lr[i] / den;
+  float fl;
+  bool out;
+  ray_bounds(c, v, box, r2, aabb, nl, fl, out);
+  ft = n - 1e-3f;
+  inside = nl < ft && ft < fl && !out;
+}
+
 __global__ __launch_bounds__(256) void light_prep_kernel(mli_light_visibility_args a) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.R) return;
-  float lr[3], c[3], v[3];
+  float c[3], ip[3], v[3];
   for (int i = 0; i < 3; ++i) {
     c[i] = a.pts_light[3 * r + i];
-    lr[i] = a.inter_pts[3 * r + i] - c[i];
+    ip[i] = a.inter_pts[3 * r + i];
   }
-  const float n = sqrtf((lr[0] * lr[0] + lr[1] * lr[1]) + lr[2] * lr[2]);
-  const float den = fmaxf(n, 1e-12f);  // F.normalize
-  for (int i = 0; i < 3; ++i) {
-    v[i] = lr[i] / den;
-    a.light_unit[3 * r + i] = v[i];
-  }
-  float nl, fl;
-  bool out;
-  ray_bounds(c, v, a.vis_box, a.vis_r2, a.aabb, nl, fl, out);
-  const float ft = n - 1e-3f;
+  float nl, ft;
+  bool inside;
+  light_ray(c, ip, a.vis_box, a.vis_r2, a.aabb, v, nl, ft, inside);
+  for (int i = 0; i < 3; ++i) a.light_unit[3 * r + i] = v[i];
   a.near_l[r] = nl;
   a.far_t[r] = ft;
-  a.inside[r] = (nl < ft && ft < fl && !out) ? 1 : 0;
+  a.inside[r] = inside ? 1 : 0;
 }
 
-// visibility, normal x light, pseudo shading (model.py:169-184, :330-334)
+// visibility, normal x light, pseudo shading of one light ray (model.py:169-184, :330-334) from its
+// hit flag, `inside`, the composited gradient g and the light direction lu.  One definition for
+// light_finalize_kernel and shadow_pairs_kernel.
+MLI_FI void light_shade(bool hit, bool inside, const float (&g)[3], const float (&lu)[3], float gamma, bool& vis,
+                        float& nxl, float& sh) {
+  vis = !hit || !inside;
+  const float g0 = -g[0], g1 = -g[1], g2 = -g[2];
+  const float gn = fmaxf(sqrtf((g0 * g0 + g1 * g1) + g2 * g2), 1e-12f);
+  const float dot = ((g0 / gn) * lu[0] + (g1 / gn) * lu[1]) + (g2 / gn) * lu[2];
+  nxl = fmaxf(dot, 0.0f);
+  sh = nxl * (vis ? 1.0f : 0.0f);
+  if (gamma != 0.0f) sh = powf(sh, 1.0f / gamma);
+}
+
 __global__ __launch_bounds__(256) void light_finalize_kernel(mli_light_visibility_args a, const uint8_t* hit) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.R) return;
-  const bool vis = !hit[r] || !a.inside[r];
-  const float g0 = -a.gradient[3 * r], g1 = -a.gradient[3 * r + 1], g2 = -a.gradient[3 * r + 2];
-  const float gn = fmaxf(sqrtf((g0 * g0 + g1 * g1) + g2 * g2), 1e-12f);
-  const float dot = ((g0 / gn) * a.light_unit[3 * r] + (g1 / gn) * a.light_unit[3 * r + 1]) +
-                    (g2 / gn) * a.light_unit[3 * r + 2];
-  const float nxl = fmaxf(dot, 0.0f);
-  float sh = nxl * (vis ? 1.0f : 0.0f);
-  if (a.gamma != 0.0f) sh = powf(sh, 1.0f / a.gamma);
+  const float g[3] = {a.gradient[3 * r], a.gradient[3 * r + 1], a.gradient[3 * r + 2]};
+  const float lu[3] = {a.light_unit[3 * r], a.light_unit[3 * r + 1], a.light_unit[3 * r + 2]};
+  bool vis;
+  float nxl, sh;
+  light_shade(hit[r] != 0, a.inside[r] != 0, g, lu, a.gamma, vis, nxl, sh);
   a.visibility[r] = vis ? 1 : 0;
   a.normal_x_light[r] = nxl;
   a.pseudo_shading[r] = sh;
+}
+
+// The light half for all (light, ray) pairs p = l * R + r in one launch (include/mli_relight.h):
+// one wave = 32 consecutive pairs (the lane halves split the hash levels, as trace_kernel); each
+// lane forms its light ray in registers (light_ray), traces it (trace_ray) and the h == 0 lanes
+// shade (light_shade) -- no scratch arrays, no launch per light.  A tile may straddle two lights
+// (r = p % R per lane) and the end of the pairs (index clamped, nothing stored).  A pair's result
+// does not depend on its tile mates: sdf_point has no cross-ray term, so each row l
+// equals the per-light kernels' output bit for bit.
+__global__ __launch_bounds__(256) void shadow_pairs_kernel(mli_light_shadows_args a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  load_weights(lds, a.wsdf);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = lane & 31, h = lane >> 5;
+  const int64_t n = (int64_t)a.L * a.R;  // <= INT32_MAX (host check)
+  const int tiles = (int)((n + 31) >> 5);
+  for (int tile = blockIdx.x * SDF_WAVES + wave; tile < tiles; tile += gridDim.x * SDF_WAVES) {
+    const int64_t p = (int64_t)tile * 32 + c;
+    const bool valid = p < n;
+    const int64_t pp = valid ? p : n - 1;
+    const int r = (int)(pp % a.R);
+    float o[3], ip[3], v[3];
+    for (int i = 0; i < 3; ++i) {
+      o[i] = a.pts_light[3 * pp + i];
+      ip[i] = a.inter_pts[3 * r + i];
+    }
+    float nl, ft;
+    bool inside, live;
+    light_ray(o, ip, a.vis_box, a.vis_r2, a.aabb, v, nl, ft, inside);
+    trace_ray(lds, a.table, a.levels, a.active_levels, a.iters, lane, o[0], o[1], o[2], v[0], v[1], v[2], nl, ft, nl,
+              live);
+    if (valid && h == 0) {
+      const float g[3] = {a.gradient[3 * r], a.gradient[3 * r + 1], a.gradient[3 * r + 2]};
+      bool vis;
+      float nxl, sh;
+      light_shade(live, inside, g, v, a.gamma, vis, nxl, sh);
+      a.visibility[p] = vis ? 1 : 0;
+      a.normal_x_light[p] = nxl;
+      a.pseudo_shading[p] = sh;
+    }
+  }
 }
 
 }  // namespace
@@ -1459,4 +1532,51 @@ extern "C" int mli_light_visibility_workspace(const mli_light_visibility_args* a
   bytes[3] = R;          // inside
   bytes[4] = R * 3 * 4;  // inter_pts
   return 0;
+}
+
+// ================================================================ include/mli_relight.h
+extern "C" int mli_relight_abi_version(void) { return MLI_RELIGHT_ABI_VERSION; }
+
+// the trace_kernel grid rule: 32 * SDF_WAVES rays (pairs) per workgroup, at most 2048 workgroups
+static int trace_blocks(int64_t n) {
+  const int64_t b = (n + 32 * SDF_WAVES - 1) / (32 * SDF_WAVES);
+  return b > 2048 ? 2048 : (int)b;
+}
+
+extern "C" int mli_camera_hit(const mli_camera_hit_args* a, mli_stream_t s) {
+  if (a->R <= 0) return 0;
+  if (a->camera_ray_type < 0 || a->camera_ray_type > 2 || a->iters < 0) return (int)hipErrorInvalidValue;
+  if (!a->center || !a->ray_unit || !a->inter_dist || !a->inter_mask || !a->inter_pts)
+    return (int)hipErrorInvalidValue;
+  if (a->camera_ray_type != 2 && !a->blend_dist) return (int)hipErrorInvalidValue;
+  if (a->camera_ray_type != 1 && (!a->near_ || !a->far_ || !a->table || !a->wsdf)) return (int)hipErrorInvalidValue;
+  const hipStream_t st = (hipStream_t)s;
+  if (a->camera_ray_type == 1) {
+    mli_light_visibility_args v{};  // blend_z_kernel reads only the fields set here
+    v.R = a->R;
+    v.center = a->center;
+    v.ray_unit = a->ray_unit;
+    v.blend_dist = a->blend_dist;
+    v.inter_dist = a->inter_dist;
+    v.inter_mask = a->inter_mask;
+    v.inter_pts = a->inter_pts;
+    hipLaunchKernelGGL(blend_z_kernel, dim3((a->R + 255) / 256), dim3(256), 0, st, v);
+  } else {
+    TraceArgs t{a->R, a->iters, a->active_levels, a->center, a->ray_unit, a->near_, a->far_,
+                a->camera_ray_type == 0 ? a->blend_dist : nullptr, a->table, a->levels, a->wsdf,
+                a->inter_dist, a->inter_mask, a->inter_pts};
+    hipLaunchKernelGGL(trace_kernel, dim3(trace_blocks(a->R)), dim3(256), LDS_SDF, st, t);
+  }
+  MLI_LAUNCH_CHECK();
+}
+
+extern "C" int mli_light_shadows(const mli_light_shadows_args* a, mli_stream_t s) {
+  if (a->L <= 0 || a->R <= 0) return 0;
+  if (a->iters < 0 || (int64_t)a->L * a->R > INT32_MAX) return (int)hipErrorInvalidValue;
+  if (!a->pts_light || !a->inter_pts || !a->gradient || !a->table || !a->wsdf || !a->visibility ||
+      !a->normal_x_light || !a->pseudo_shading)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(shadow_pairs_kernel, dim3(trace_blocks((int64_t)a->L * a->R)), dim3(256), LDS_SDF,
+                     (hipStream_t)s, *a);
+  MLI_LAUNCH_CHECK();
 }

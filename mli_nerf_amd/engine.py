@@ -613,27 +613,32 @@ class RenderEngine(_Lanes):
         """Forget a deferred composite_loss whose step failed (its loss slot is not valid)."""
         self._lane.step.pop("cl_deferred", None)
 
-    @torch.no_grad()
-    def light_visibility(self, rays, comp, iters=20):
-        """get_light_visibility (NeuralLumen/model.py:133-184): adds visibility, normal_x_light,
-        pseudo_shading, inter_dist, inter_mask ([R,1]) to the composite dict."""
+    def _vis_config(self):
+        """cfg.light_visibility as the kernels take it: (camera_ray_type 0..2, box flag, radius^2, gamma)."""
         vis = self.cfg.light_visibility
         if vis.get("type", "sphere_tracing") != "sphere_tracing":
             raise NotImplementedError("light visibility type %r (only 'sphere_tracing', the configs' choice, "
                                       "is built)" % vis.get("type"))
         kind = {"blend_z_sphere_tracing": 0, "blend_z": 1, "sphere_tracing": 2}[vis["camera_ray_type"]]
+        box = vis.get("bounding", "sphere") == "box"
+        r2 = float(np.float32(float(vis.get("radius", 1.0)) ** 2))
+        return kind, box, r2, float(vis.get("gamma") or 0.0)
+
+    @torch.no_grad()
+    def light_visibility(self, rays, comp, iters=20):
+        """get_light_visibility (NeuralLumen/model.py:133-184): adds visibility, normal_x_light,
+        pseudo_shading, inter_dist, inter_mask ([R,1]) to the composite dict."""
+        kind, box, r2, gamma = self._vis_config()
         R = rays["center"].shape[0]
         f = lambda *shape: torch.empty(*shape, device=self.device)  # noqa: E731
         u8 = lambda n: torch.empty(n, 1, dtype=torch.uint8, device=self.device)  # noqa: E731
         o = dict(inter_dist=f(R, 1), inter_mask=u8(R), visibility=u8(R), normal_x_light=f(R, 1),
                  pseudo_shading=f(R, 1))
         scratch = dict(light_unit=f(R, 3), near_l=f(R), far_t=f(R), inside=u8(R), inter_pts=f(R, 3))
-        box = vis.get("bounding", "sphere") == "box"
-        r2 = float(np.float32(float(vis.get("radius", 1.0)) ** 2))
         L.call("mli_light_visibility", L.LightVisibilityArgs(
             R, L.ptr(rays["center"]), L.ptr(rays["ray_unit"]), L.ptr(rays["pts_light"]), L.ptr(rays["near"]),
             L.ptr(rays["far"]), L.ptr(comp["blend_dist"]), L.ptr(comp["gradient"]), kind, iters, 1 if box else 0,
-            r2, (C.c_float * 6)(*self.cfg.aabb), float(vis.get("gamma") or 0.0), L.ptr(self.table16), self.levels,
+            r2, (C.c_float * 6)(*self.cfg.aabb), gamma, L.ptr(self.table16), self.levels,
             int(self.active_levels), L.ptr(self.wsdf), L.ptr(scratch["light_unit"]), L.ptr(scratch["near_l"]),
             L.ptr(scratch["far_t"]), L.ptr(scratch["inside"]), L.ptr(o["inter_dist"]), L.ptr(o["inter_mask"]),
             L.ptr(scratch["inter_pts"]), L.ptr(o["visibility"]), L.ptr(o["normal_x_light"]),
@@ -670,6 +675,70 @@ class RenderEngine(_Lanes):
         if self.cfg.light_visibility and not training:
             self.light_visibility(rays, comp)
         return rays, dists, fld, hd, comp
+
+    @torch.no_grad()
+    def light_points(self, pose_lights, R):
+        """pts_light [L,R,3] of L w2l poses [L,3,4] (mli_light_points): row l holds the bits rays()
+        writes to its pts_light under pose_lights[l]."""
+        w2l = pose_lights.to(self.device, torch.float32).contiguous()
+        n = w2l.shape[0]
+        pl = self._buf("pts_lights", (n, R, 3))
+        L.call("mli_light_points", L.LightPointsArgs(n, R, L.ptr(w2l), L.ptr(pl)))
+        return pl
+
+    @torch.no_grad()
+    def lights_visibility(self, rays, pts_lights, comps, iters=20):
+        """get_light_visibility (NeuralLumen/model.py:133-184) of one view under L lights: the camera
+        intersection once (mli_camera_hit; it reads the first composite's blend_dist, which no light
+        changes) and every light's rays in one launch (mli_light_shadows).  Adds to composite dict l what
+        light_visibility() adds under light l; inter_dist / inter_mask are one tensor for all."""
+        kind, box, r2, gamma = self._vis_config()
+        n, R = pts_lights.shape[0], rays["center"].shape[0]
+        f = lambda *shape: torch.empty(*shape, device=self.device)  # noqa: E731
+        u8 = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=self.device)  # noqa: E731
+        inter_dist, inter_mask, inter_pts = f(R, 1), u8(R, 1), f(R, 3)
+        L.call("mli_camera_hit", L.CameraHitArgs(
+            R, L.ptr(rays["center"]), L.ptr(rays["ray_unit"]), L.ptr(rays["near"]), L.ptr(rays["far"]),
+            L.ptr(comps[0]["blend_dist"]), kind, iters, L.ptr(self.table16), self.levels, int(self.active_levels),
+            L.ptr(self.wsdf), L.ptr(inter_dist), L.ptr(inter_mask), L.ptr(inter_pts)))
+        vis, nxl, sh = u8(n, R, 1), f(n, R, 1), f(n, R, 1)
+        L.call("mli_light_shadows", L.LightShadowsArgs(
+            n, R, L.ptr(pts_lights), L.ptr(inter_pts), L.ptr(comps[0]["gradient"]), 1 if box else 0, r2,
+            (C.c_float * 6)(*self.cfg.aabb), gamma, iters, L.ptr(self.table16), self.levels,
+            int(self.active_levels), L.ptr(self.wsdf), L.ptr(vis), L.ptr(nxl), L.ptr(sh)))
+        vis, inter_mask = vis.bool(), inter_mask.bool()
+        for l, comp in enumerate(comps):
+            comp.update(inter_dist=inter_dist, inter_mask=inter_mask, visibility=vis[l], normal_x_light=nxl[l],
+                        pseudo_shading=sh[l])
+        return comps
+
+    SHARED_MAPS = ("opacity", "gradient", "depth", "blend_dist")   # composite outputs no light changes
+
+    def render_lights(self, data, pose_lights, s_var, progress, W=512):
+        """One view under L lights (eval), the geometry computed once: geometry() and mli_light_points,
+        then per light only what depends on it -- heads() (through SH(pts_light)) and composite() --
+        and with visibility on one camera intersection and one launch for all light rays
+        (lights_visibility).  ``pose_lights`` [L,3,4]; data["pose_light"] is not read.  Returns (rays,
+        dists, fld, comps): comps[l] holds the keys, dtypes and bits of render()'s composite dict
+        under light l; the light-independent maps (SHARED_MAPS, inter_dist, inter_mask, weights) are
+        the first light's tensors in every dict.  On the current lane and stream."""
+        step = self._lane.step
+        step["__gen"] = step.get("__gen", 0) + 1
+        rays, dists, fld = self.geometry(dict(data, pose_light=pose_lights[:1]), W, False)
+        pl = self.light_points(pose_lights, rays["center"].shape[0])
+        comps = []
+        for l in range(pl.shape[0]):
+            rl = dict(rays, pts_light=pl[l])
+            hd = self.heads(rl, dists, fld, False, s_var, progress)
+            # (the shared maps depend on the weights, dists and gradients alone: written once)
+            out = self._composite_out(dists, extras=l == 0)
+            L.call("mli_composite_fwd", self._composite_args(rl, dists, fld, hd, s_var, progress, out))
+            if l:
+                out.update({k: comps[0][k] for k in self.SHARED_MAPS if k in comps[0]})
+            comps.append(out)
+        if self.cfg.light_visibility:
+            self.lights_visibility(rays, pl, comps)
+        return rays, dists, fld, comps
 
     # ------------------------------------------------------------------ backward
     @staticmethod

@@ -473,6 +473,26 @@ class Model(torch.nn.Module):
         Under an initialised process group with world > 1 (and shard=True) each rank renders
         one contiguous tile of the frame and ONE all_gather assembles it, so
         every rank returns the full maps."""
+        return self._inference(data, shard, None)[0]
+
+    @torch.no_grad()
+    def inference_lights(self, data, pose_lights, shard=True):
+        """One view under L lights: a list of L dicts, dict l with exactly the keys, shapes, dtypes
+        and bits of ``inference({**data, "pose_light": pose_lights[l:l+1]})``, with everything that
+        does not depend on the light -- rays, the sampling rounds, the FIELD pass, the NeuS weights,
+        the camera intersection -- computed once per chunk (RenderEngine.render_lights).
+        ``pose_lights`` [L,3,4] (w2l); data["pose_light"] is not read.  Chunks, padding, the
+        two-lane pipelining and the single all_gather (L x the packed channels per ray) are
+        inference()'s."""
+        if not torch.is_tensor(pose_lights) or pose_lights.dim() != 3 or tuple(pose_lights.shape[1:]) != (3, 4):
+            raise ValueError("inference_lights: pose_lights must be a [L,3,4] tensor, got %s" % (
+                tuple(pose_lights.shape) if torch.is_tensor(pose_lights) else type(pose_lights).__name__,))
+        if pose_lights.shape[0] == 0:
+            raise ValueError("inference_lights: pose_lights holds no light (L == 0)")
+        return self._inference(data, shard, pose_lights)
+
+    def _inference(self, data, shard, pose_lights):
+        """inference() (pose_lights None: one dict, data's own light) / inference_lights()."""
         from . import shard as sh
         self.eval()
         self.prepare()
@@ -491,6 +511,9 @@ class Model(torch.nn.Module):
         vis = self.pcfg.light_visibility is not None
         step = 256 // math.gcd(N, 256)
         dev = self.flat.device
+        n_lights = 1 if pose_lights is None else pose_lights.shape[0]
+        if pose_lights is not None:
+            pose_lights = pose_lights.to(dev, torch.float32).contiguous()
         parts = []
         # Two chunks in flight on two streams, each with its own engine buffer lane: one
         # chunk's gather-bound sampling / FIELD kernels overlap the other's MFMA-bound heads.
@@ -506,29 +529,37 @@ class Model(torch.nn.Module):
                 lane = i % 2 if self.pipeline_chunks else 0
                 with torch.cuda.stream(self._streams[lane]), self.engine.lane(lane):
                     ridx = torch.arange(start, start + Rp, device=dev).clamp_(max=start + R - 1)[None]
-                    d = dict(pose=data["pose"], intr=data["intr"], pose_light=data["pose_light"], ray_idx=ridx)
-                    st = self.engine.render(d, self.s_var.detach(), self.progress, False, u=None, W=W)
-                    parts.append(sh.pack(st[4], vis)[:R])
+                    if pose_lights is None:
+                        d = dict(pose=data["pose"], intr=data["intr"], pose_light=data["pose_light"], ray_idx=ridx)
+                        st = self.engine.render(d, self.s_var.detach(), self.progress, False, u=None, W=W)
+                        parts.append(sh.pack(st[4], vis)[:R])
+                    else:
+                        d = dict(pose=data["pose"], intr=data["intr"], ray_idx=ridx)
+                        comps = self.engine.render_lights(d, pose_lights, self.s_var.detach(), self.progress, W)[3]
+                        parts.append(sh.pack_lights(comps, vis)[:R])
         finally:
             for s in self._streams:
                 main.wait_stream(s)
         for p in parts:
             p.record_stream(main)
-        local = torch.cat(parts, 0) if parts else torch.zeros(0, sh.n_channels(vis), device=dev)
+        local = torch.cat(parts, 0) if parts else torch.zeros(0, n_lights * sh.n_channels(vis), device=dev)
         packed = sh.gather_tiles(local, n_pix, world, group) if world > 1 else local
-        out = {k: v.contiguous()[None] for k, v in sh.unpack(packed, vis).items()}
         rot = data["pose"][..., :3, :3]
-        normal_cam = -out["gradient"] @ rot.transpose(-1, -2)
 
         def full(x):
             return x.unflatten(1, (H, W)).moveaxis(-1, 1)
-        out.update(rgb_map=full(out["rgb"]), opacity_map=full(out["opacity"]), depth_map=full(out["depth"]),
-                   normal_map=full(normal_cam))
-        for k in ("o_r", "o_s", "o_re"):
-            out[k + "_map"] = full(out[k])
-        if vis:  # NeuralLumen/model.py:78-83
-            for k in ("visibility", "normal_x_light", "pseudo_shading", "inter_dist", "inter_mask"):
-                out[k + "_map"] = full(out[k]).float()
-            out["visibility"] = out["visibility"] > 0.5
-            out["inter_mask"] = out["inter_mask"] > 0.5
-        return out
+        outs = []
+        for unpacked in sh.unpack_lights(packed, n_lights, vis):
+            out = {k: v.contiguous()[None] for k, v in unpacked.items()}
+            normal_cam = -out["gradient"] @ rot.transpose(-1, -2)
+            out.update(rgb_map=full(out["rgb"]), opacity_map=full(out["opacity"]), depth_map=full(out["depth"]),
+                       normal_map=full(normal_cam))
+            for k in ("o_r", "o_s", "o_re"):
+                out[k + "_map"] = full(out[k])
+            if vis:  # NeuralLumen/model.py:78-83
+                for k in ("visibility", "normal_x_light", "pseudo_shading", "inter_dist", "inter_mask"):
+                    out[k + "_map"] = full(out[k]).float()
+                out["visibility"] = out["visibility"] > 0.5
+                out["inter_mask"] = out["inter_mask"] > 0.5
+            outs.append(out)
+        return outs

@@ -6,7 +6,8 @@ per camera, seed 999), ``limitedlights`` and ``singlelight`` (limitedlights with
 ``get_random_other_index`` of ``projects/NeuralLumen/utils/utils.py:230-252``; the image writer
 ``preprocess_image`` of ``imaginaire/utils/visualization.py:29-41``.
 
-For every (camera, light) pair one ``Model.inference`` renders the full frame with the light
+For every (camera, light) pair one ``Model.inference`` (with ``share_geometry``: one
+``Model.inference_lights`` per camera view) renders the full frame with the light
 visibility pass on (the GPU renderer: sampling, FIELD, heads, composite, sphere-traced camera and
 light rays, tile-sharded over ranks when a process group is up) at iteration ``sys.maxsize``
 (mode 'test': the NeuS anneal finished).  The maps go to ``<output_dir>/<camera>/<light>_*.png``
@@ -88,10 +89,40 @@ def save_image(image, path, from_range=(0, 1)):
     Image.fromarray(a[:, :, 0] if a.shape[2] == 1 else a, mode="L" if a.shape[2] == 1 else "RGB").save(path)
 
 
+def _view_key(data):
+    """What makes two frames one view: the bits of pose and intr, and the image size."""
+    def raw(t):
+        return (tuple(t.shape), str(t.dtype), t.detach().cpu().contiguous().numpy().tobytes())
+    size = tuple(data["image"].shape[-2:]) if torch.is_tensor(data.get("image")) else None
+    return raw(data["pose"]), raw(data["intr"]), size
+
+
+def render_shared(model, datas):
+    """The ``Model.inference`` outputs of ``datas`` (one dict per light, in order), the frames that
+    are one view (_view_key) rendered together by one ``Model.inference_lights`` call -- the geometry
+    of the view computed once -- and every other frame by ``inference``."""
+    groups = {}
+    for i, d in enumerate(datas):
+        groups.setdefault(_view_key(d), []).append(i)
+    outs = [None] * len(datas)
+    for idx in groups.values():
+        if len(idx) == 1:
+            outs[idx[0]] = model.inference(datas[idx[0]])
+            continue
+        lights = torch.cat([datas[i]["pose_light"].reshape(1, 3, 4) for i in idx], 0)
+        for i, out in zip(idx, model.inference_lights(datas[idx[0]], lights)):
+            outs[i] = out
+    return outs
+
+
 @torch.no_grad()
 def test_all_light(trainer, data_loader, output_dir=None, mode="test", dataset_type="pair", sample_num=4, seed=999,
-                   save_images=True):
-    """trainer.py:216-316.  ``data_loader``: a DataLoader (its ``.dataset``) or the Dataset."""
+                   save_images=True, share_geometry=False):
+    """trainer.py:216-316.  ``data_loader``: a DataLoader (its ``.dataset``) or the Dataset.
+    ``share_geometry``: the lights of a camera that share its view (unpair / limitedlights: all of
+    them; pair: the frames of a camera_index whose pose, intr and size are bitwise equal) are
+    rendered by one ``Model.inference_lights`` call (render_shared); the files written are the same,
+    byte for byte."""
     model = trainer.model
     if model.pcfg.light_visibility is None:
         raise ValueError("test_all_light needs model.light_visibility.enabled (its maps: visibility, "
@@ -109,6 +140,7 @@ def test_all_light(trainer, data_loader, output_dir=None, mode="test", dataset_t
             os.makedirs(cam_dir, exist_ok=True)
             results_light = {}
             data_input = None
+            datas, outs = [], []
             for light in info[cam]:
                 if dataset_type == "pair":
                     data = dataset[info[cam][light]]
@@ -121,7 +153,12 @@ def test_all_light(trainer, data_loader, output_dir=None, mode="test", dataset_t
                 data = {k: v[None] if torch.is_tensor(v) else v for k, v in data.items()}
                 data = trainer.start_of_iteration(data, current_iteration=c_iter)
                 trainer._start_of_iteration()
-                out = model.inference(data)
+                datas.append(data)
+                if not share_geometry:   # rendered as enumerated, one light at a time
+                    outs.append(model.inference(data))
+            if share_geometry:
+                outs = render_shared(model, datas)
+            for light, data, out in zip(info[cam], datas, outs):
                 pre = str(light) + "_"
 
                 def save(img, name, from_range=(0, 1)):

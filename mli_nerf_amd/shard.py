@@ -48,6 +48,20 @@ def unpack(packed, vis=False):
     return res
 
 
+def pack_lights(outs, vis=False):
+    """One view under L lights: L dicts of [R, c] tensors -> [R, L * n_channels] fp32, light l in
+    columns [l * n_channels, (l + 1) * n_channels) -- what one gather_tiles call carries."""
+    return torch.cat([pack(o, vis) for o in outs], dim=1)
+
+
+def unpack_lights(packed, n_lights, vis=False):
+    """The inverse of pack_lights: a list of n_lights dicts of [R, c] views."""
+    c = n_channels(vis)
+    if packed.shape[1] != n_lights * c:
+        raise ValueError("unpack_lights: %d columns are not %d lights x %d channels" % (packed.shape[1], n_lights, c))
+    return [unpack(packed[:, l * c:(l + 1) * c], vis) for l in range(n_lights)]
+
+
 def gather_tiles(local, n, world, group=None):
     """All ranks' [hi-lo, C] tiles -> the full [n, C] on every rank (one all_gather)."""
     import torch.distributed as dist

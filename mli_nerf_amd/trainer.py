@@ -25,6 +25,7 @@ Construction follows the plugin call ``trainer_lib.Trainer(cfg, is_inference=...
 import importlib
 import math
 import os
+import sys
 
 import torch
 import torch.nn.functional as F
@@ -1191,12 +1192,26 @@ class Trainer:
                                   video_content=video_content, show_pbar=show_pbar)
 
     def test_all_light(self, data_loader, output_dir=None, mode="test", dataset_type="pair", sample_num=4,
-                       seed=999):
+                       seed=999, share_geometry=False):
         """NeuralLumen/trainer.py:216-316: every (camera, light) pair of the enumeration
         (pair / unpair / limitedlights) rendered with the light-visibility pass, the maps saved as
-        PNGs and ``results_all.pt`` for scripts/pseudo_label.py (see mli_nerf_amd.relight)."""
+        PNGs and ``results_all.pt`` for scripts/pseudo_label.py (see mli_nerf_amd.relight).
+        ``share_geometry``: the lights of one camera view in one ``Model.inference_lights`` call."""
         from . import relight
-        return relight.test_all_light(self, data_loader, output_dir, mode, dataset_type, sample_num, seed)
+        return relight.test_all_light(self, data_loader, output_dir, mode, dataset_type, sample_num, seed,
+                                      share_geometry=share_geometry)
+
+    def relight(self, data, pose_lights):
+        """One view under the lights ``pose_lights`` [L,3,4] with the trained model, as test_all_light
+        renders it (iteration sys.maxsize: the NeuS anneal and the coarse-to-fine schedule finished):
+        the list of ``Model.inference_lights``.  ``current_iteration`` is restored."""
+        saved = self.current_iteration
+        try:
+            data = self.start_of_iteration(data, current_iteration=sys.maxsize)
+            self._start_of_iteration()
+            return self.model.inference_lights(data, pose_lights)
+        finally:
+            self.current_iteration = saved
 
     def make_pseudo_labels(self, data_loader, output_dir, setting="pair", images=True, **test_all_light_kwargs):
         """From a stage-a model to the stage-b label file in one call: ``test_all_light`` (writes
