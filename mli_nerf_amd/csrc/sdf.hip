@@ -512,14 +512,13 @@ __global__ __launch_bounds__(256) void hashgrid_kernel(mli_hashgrid_args a) {
 }
 
 // ---------------------------------------------------------------- SDF layer-0 packing
-// W0 = g0 * v0 / ||v0||_row (torch weight_norm dim=0); fp16 fragments of the 128 encoding
-// columns (NAT order, k = 16q + 8h + j -> input column 3 + k) and fp32 row constants in
-// accumulator order: b0, W0[:,0], W0[:,1], W0[:,2], w_sdf.
-__global__ __launch_bounds__(256) void pack_sdf_kernel(mli_pack_sdf_args a) {
-  const int n = blockIdx.x;  // output row 0..255
-  __shared__ float red[256];
+// g0[n] / ||v0[n, :]|| of layer-0 row n by a 256-thread workgroup (red: LDS [256]).  One definition
+// for both layer-0 packers: the forward block and the W0_enc^T block hold v * scale with the same
+// scale, so the same fp16 weight bit for bit (a sum of the squares in another order moves the
+// scale by an fp32 ulp in half the rows, and a few fp16 roundings with it).
+MLI_FI float sdf_row_scale(const float* v0, const float* g0, int n, float* red) {
   const int tid = threadIdx.x;
-  const float* vrow = a.v0 + n * 131;
+  const float* vrow = v0 + n * 131;
   float ss = 0.f;
   for (int k = tid; k < 131; k += 256) ss += vrow[k] * vrow[k];
   red[tid] = ss;
@@ -528,14 +527,33 @@ __global__ __launch_bounds__(256) void pack_sdf_kernel(mli_pack_sdf_args a) {
     if (tid < s) red[tid] += red[tid + s];
     __syncthreads();
   }
-  const float scale = a.g0[n] / sqrtf(red[0]);
+  const float scale = g0[n] / sqrtf(red[0]);
+  __syncthreads();  // red may be reused for the next row
+  return scale;
+}
+
+// fp16(v * scale), rounded once from the exact product (the product of two floats is exact in
+// double).  Spelled out because `(f16)(v * scale)` compiles to v_fma_mixlo_f16 (one rounding) in one
+// place and to v_mul_f32 + v_cvt_pk_f16_f32 (two roundings) in another, 1 fp16 ulp apart in about
+// 6e-5 of the elements; the forward block has always been the once-rounded one.
+MLI_FI f16 sdf_w16(float v, float scale) { return (f16)((double)v * (double)scale); }
+
+// W0 = g0 * v0 / ||v0||_row (torch weight_norm dim=0); fp16 fragments of the 128 encoding
+// columns (NAT order, k = 16q + 8h + j -> input column 3 + k) and fp32 row constants in
+// accumulator order: b0, W0[:,0], W0[:,1], W0[:,2], w_sdf.
+__global__ __launch_bounds__(256) void pack_sdf_kernel(mli_pack_sdf_args a) {
+  const int n = blockIdx.x;  // output row 0..255
+  __shared__ float red[256];
+  const int tid = threadIdx.x;
+  const float* vrow = a.v0 + n * 131;
+  const float scale = sdf_row_scale(a.v0, a.g0, n, red);
   const int t = n >> 5, r = n & 31;
   // fragments: thread k-index over 128 enc columns
   if (tid < 128) {
     const int k = tid, q = k >> 4, hh = (k >> 3) & 1, j = k & 7;
     const int lanei = hh * 32 + r;
     f16* dst = reinterpret_cast<f16*>(a.dst + (t * 8 + q) * 1024 + lanei * 16) + j;
-    *dst = (f16)(vrow[3 + k] * scale);
+    *dst = sdf_w16(vrow[3 + k], scale);
   }
   if (tid == 0) {
     // locate (h, i) with acc_row(i, h) == r
@@ -563,18 +581,21 @@ constexpr int SDFT_PIECES = MLI_SDF_T_PACK_BYTES / 16;
 __global__ __launch_bounds__(256) void pack_sdf_t_kernel(mli_pack_sdf_t_args a) {
   // blockIdx.x = (u*16 + q); thread = lane*8 + j (512 elements per k-step)... 64 lanes x 8
   const int uq = blockIdx.x, u = uq >> 4, q = uq & 15;
+  // the row scales of this k-step's 16 h0 indices, exactly as pack_sdf_kernel forms them
+  __shared__ float red[256], sc[16];
+  for (int i = 0; i < 16; ++i) {
+    const float s = sdf_row_scale(a.v0, a.g0, 16 * q + i, red);
+    if (threadIdx.x == 0) sc[i] = s;
+  }
+  __syncthreads();
   for (int e = threadIdx.x; e < 512; e += blockDim.x) {
     const int lane = e >> 3, j = e & 7;
     const int rl = lane & 31, hh = lane >> 5;
     const int hr = (rl >> 2) & 1, i = (rl & 3) + 4 * (rl >> 3);
     const int qp = 2 * u + (i >> 3), level = 2 * qp + hr, f = i & 7;
     const int col = 3 + level * 8 + f;
-    const int n = k_acc(q, hh, j);  // h0 index = output row of W0
-    const float* vrow = a.v0 + n * 131;
-    float ss = 0.f;
-    for (int kk = 0; kk < 131; ++kk) ss += vrow[kk] * vrow[kk];
-    const float w = vrow[col] * (a.g0[n] / sqrtf(ss));
-    reinterpret_cast<f16*>(a.dst + uq * 1024 + lane * 16)[j] = (f16)w;
+    const int n = k_acc(q, hh, j);  // h0 index = output row of W0, in [16 q, 16 q + 16)
+    reinterpret_cast<f16*>(a.dst + uq * 1024 + lane * 16)[j] = sdf_w16(a.v0[n * 131 + col], sc[n - 16 * q]);
   }
 }
 
