@@ -268,6 +268,15 @@ typedef struct {
    * 8 b + w, dense from tile 0 on. */
   const int32_t* tile_list;
   const int32_t* n_live_tiles;
+  /* Nonzero tiles, optional (both NULL: every tile of the live rays, as above; only with the live
+   * arrays above): the padded list of mli_live_tiles.  Workgroup b returns at once when
+   * 8 b >= *n_wtiles_pad; its wave w takes list entry j = 8 b + w: the images are written at the
+   * compact tile p = wtile_list[j] (where mli_wgrad looks for them), the samples are the original
+   * tile tile_list[p], and q4 holds one item per entry, q4[j][head][257][4] (sized for S / 32
+   * entries; mli_dw4_args.wtile_rank).  A pad entry (all weights +-0) runs the same body and stores
+   * y = 0.  The tiles that are not listed are not touched: mli_live_tiles has zeroed their y rows. */
+  const int32_t* wtile_list;
+  const int32_t* n_wtiles_pad;
 } mli_rgb_fwd_args;
 #define MLI_Q4_SCALE 65536.0f
 /* ray segments per 256-sample workgroup (an upper bound; N % 32 == 0) */
@@ -275,7 +284,8 @@ typedef struct {
 int mli_rgb_fwd(const mli_rgb_fwd_args* a, mli_stream_t s);
 /* bytes[0..5]: y, feat_frag, 0, xT, masks, q4 (xT, masks 0 unless `train` = xT != NULL is
  * requested by setting a->xT to any non-NULL value before the query; q4 0 unless a->weights is
- * non-NULL, which also drops X3 from xT). */
+ * non-NULL, which also drops X3 from xT; with a->wtile_list non-NULL q4 is sized for one item per
+ * 32-sample tile). */
 int mli_rgb_fwd_workspace(const mli_rgb_fwd_args* a, int64_t* bytes);
 
 /* ---------------------------------------------------------------- compositing
@@ -331,6 +341,11 @@ typedef struct {
    * tile_list[8 b + w]; masks are read and dzT is written at the compact tile 8 b + w. */
   const int32_t* tile_list;
   const int32_t* n_live_tiles;
+  /* Nonzero tiles, optional (both NULL: every tile of the live rays; only with the live arrays
+   * above), as mli_rgb_fwd_args: wave w of workgroup b reads the masks and writes dzT at the compact
+   * tile wtile_list[8 b + w]; workgroups with 8 b >= *n_wtiles_pad return at once. */
+  const int32_t* wtile_list;
+  const int32_t* n_wtiles_pad;
 } mli_rgb_bwd_args;
 int mli_rgb_bwd(const mli_rgb_bwd_args* a, mli_stream_t s);
 /* bytes[0..1]: dzT, dz4T. */
@@ -429,6 +444,12 @@ typedef struct {
   const int32_t* tile_rank; /* live rays, optional (NULL: dense): [S/32 + 1] of mli_live_rays; the
                              (workgroup, segment) items of rays without a live tile are skipped (their
                              q4 slots were not written) */
+  const int32_t* wtile_rank; /* nonzero tiles, optional (NULL: q4 as above; only with tile_rank):
+                             [S/32 + 1] of mli_live_tiles.  q4 then holds one item per nonzero tile,
+                             q4[j][n_heads][257][4] in wtile_list order (mli_rgb_fwd_args.wtile_list),
+                             and a live ray's Q is 0 plus its items [wtile_rank[p], wtile_rank[p + N/32]),
+                             p = tile_rank[r N/32], in ascending order -- the dense sum over the ray's
+                             tiles without the +-0 terms -- before it meets dray */
 } mli_dw4_args;
 int mli_dw4(const mli_dw4_args* a, mli_stream_t s);
 /* bytes[0]: workspace (slice partials). */
@@ -469,7 +490,7 @@ int mli_live_rays(const mli_live_rays_args* a, mli_stream_t s);
  * them the nonzero tiles in compact order:
  *   wtile_list [W]        the compact positions p (ascending) whose original tile tile_list[p]
  *                         has a nonzero weight; W <= L T.  Dead and pad rays have none.  Entries
- *                         from W on are not written.
+ *                         from W on are not written (but see n_wtiles_pad).
  *   wtile_rank [S/32 + 1] entries of wtile_list below compact position p; wtile_rank[p] = W for
  *                         every p >= L T.
  * mli_wgrad streams only these tiles (mli_wgrad_args.wtile_rank / wtile_list).
@@ -486,6 +507,12 @@ struct mli_live_tiles_args_s {
   int32_t* wtile_list; int32_t* wtile_rank;
   int32_t* ticket;         /* one word, 0 between launches (scan_launch == 0) */
   int scan_launch;
+  /* Optional (NULL: as described above).  The heads take the nonzero tiles eight to a workgroup
+   * (mli_rgb_fwd_args.wtile_list): the scan then appends (-W mod 8) pad entries to wtile_list, the
+   * lowest compact positions whose tile has no nonzero weight (ascending; S/32 is a multiple of 8,
+   * so there are enough), writes W rounded up to a multiple of 8 here, and the pass also zeroes
+   * the y rows of the all-zero tiles inside live rays (the heads no longer write them). */
+  int32_t* n_wtiles_pad;
 };
 typedef struct mli_live_tiles_args_s mli_live_tiles_args;
 int mli_live_tiles(const mli_live_tiles_args* a, mli_stream_t s);

@@ -58,7 +58,7 @@ class RgbFwdArgs(C.Structure):
     _fields_ = [("R", I32), ("N", I32), ("center", P), ("ray_unit", P), ("pts_light", P),
                 ("dists", P), ("grad", P), ("h0", P), ("wfwd", P), ("y", P), ("feat_frag", P),
                 ("xT", P), ("masks", P), ("n_heads", I32), ("weights", P), ("q4", P),
-                ("tile_list", P), ("n_live_tiles", P)]
+                ("tile_list", P), ("n_live_tiles", P), ("wtile_list", P), ("n_wtiles_pad", P)]
 
 
 class CompositeArgs(C.Structure):
@@ -76,7 +76,8 @@ class CompositeBwdArgs(C.Structure):
 
 class RgbBwdArgs(C.Structure):
     _fields_ = [("R", I32), ("N", I32), ("dz4", P), ("wbwd", P), ("masks", P), ("dzT", P),
-                ("dz4T", P), ("skip_dz3", I32), ("tile_list", P), ("n_live_tiles", P)]
+                ("dz4T", P), ("skip_dz3", I32), ("tile_list", P), ("n_live_tiles", P),
+                ("wtile_list", P), ("n_wtiles_pad", P)]
 
 
 class WgradJob(C.Structure):
@@ -105,7 +106,7 @@ class WgradArgs(C.Structure):
 class Dw4Args(C.Structure):
     _fields_ = [("R", I32), ("N", I32), ("n_heads", I32), ("q4", P), ("dray", P), ("scale", F32),
                 ("dw", P * 3), ("db", P * 3), ("k_out", I32 * 3), ("workspace", P),
-                ("tile_rank", P)]
+                ("tile_rank", P), ("wtile_rank", P)]
 
 
 class LiveRaysArgs(C.Structure):
@@ -115,7 +116,8 @@ class LiveRaysArgs(C.Structure):
 
 class LiveTilesArgs(C.Structure):
     _fields_ = [("comp", CompositeArgs), ("y", P), ("flags", P), ("tile_list", P), ("tile_rank", P),
-                ("n_live_tiles", P), ("wtile_list", P), ("wtile_rank", P), ("ticket", P), ("scan_launch", I32)]
+                ("n_live_tiles", P), ("wtile_list", P), ("wtile_rank", P), ("ticket", P), ("scan_launch", I32),
+                ("n_wtiles_pad", P)]
 
 
 Q4_SCALE = 65536.0  # include/mli_hip.h MLI_Q4_SCALE

@@ -487,7 +487,14 @@ MLI_FI void q4_tile(const mli_rgb_fwd_args& a, uint8_t* lds, const half8 (&X)[19
     const int nthr = ROLE == STORE ? G::THREADS / 2 : G::THREADS;
     const int tid = ROLE == STORE ? threadIdx.x - G::THREADS / 2 : threadIdx.x;
     f32x4* qb = reinterpret_cast<f32x4*>(a.q4);
-    for (int it = tid; it < nseg * 257; it += nthr) {
+    // nonzero tiles (wtile_list): a ray's tiles may sit in two workgroups, so every wave's Q goes
+    // out as the item of its list entry t0 + w and mli_dw4 forms the per-ray sums
+    for (int it = tid; it < (a.wtile_list ? G::NW * 257 : 0); it += nthr) {
+      const int w = it / 257, row = it - w * 257;
+      gstore_nt(qb + ((size_t)(t0 + w) * a.n_heads + hd) * 257 + row,
+                *reinterpret_cast<const f32x4*>(q4_park(w) + row * 16));
+    }
+    for (int it = tid; it < (a.wtile_list ? 0 : nseg * 257); it += nthr) {
       const int seg = it / 257, row = it - seg * 257;
       // the segment's q4 item: [wg][seg] of the dense order; live rays (tile_list, 256 % N == 0: the
       // workgroup holds whole rays, segs per workgroup = rays per workgroup): the item of the
@@ -505,6 +512,15 @@ MLI_FI void q4_tile(const mli_rgb_fwd_args& a, uint8_t* lds, const half8 (&X)[19
   block_sync();  // the Q park is free again
 }
 
+// The image position of wave `w` of this workgroup: its slot 8 b + w, or (list: the heads take the
+// nonzero tiles, mli_rgb_fwd_args.wtile_list) the compact position the list holds at that slot --
+// one ordinary load, made wave-uniform once at entry.
+template <class G>
+MLI_FI int heads_tile(const int32_t* list, int w) {
+  const int j = blockIdx.x * G::NW + w;
+  return list ? __builtin_amdgcn_readfirstlane(list[j]) : j;
+}
+
 // ---------------------------------------------------------------------- forward
 // chunk sizes in consumption order: SDF layer 1 (8 x KS 16), then per head L0 (8 x KS 19),
 // L1..L3 (24 x KS 16), L4 (1 x KS 16)
@@ -515,10 +531,11 @@ MLI_FI void rgb_fwd_body(const mli_rgb_fwd_args& a, uint8_t* lds) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
   const int S = a.R * a.N;
-  // `tile`: the wave's position in the images the weight gradients read (x0, X1..X3, masks);
+  // `tile`: the wave's position in the images the weight gradients read (x0, X1..X3, masks) -- its
+  // slot 8 b + w, or (nonzero tiles: wtile_list) the compact position the list holds there;
   // `tile_o`: the 32 samples it works on -- the same tile, or (live rays: tile_list) the original
-  // tile tile_list[tile]: rays, dists, grad, h0, weights, y and the q4 item go by it
-  const int tile = blockIdx.x * G::NW + wave;
+  // tile tile_list[tile]: rays, dists, grad, h0, weights, y and the ray's q4 item go by it
+  const int tile = heads_tile<G>(PQ ? a.wtile_list : nullptr, wave);
   const int tile_o = (PQ && a.tile_list) ? __builtin_amdgcn_readfirstlane(a.tile_list[tile]) : tile;
   const int m = tile_o * 32 + c;
   const int r = m / a.N, k = m - r * a.N;
@@ -529,6 +546,9 @@ MLI_FI void rgb_fwd_body(const mli_rgb_fwd_args& a, uint8_t* lds) {
   constexpr int FKS = PQ ? G::FEAT_KS : (!TRAIN ? G::FEAT_KS_EVAL : 0);
   constexpr int FOFF = PQ ? G::LDS_FWD_PQ : G::LDS_FWD;
   const float wgt = PQ ? a.weights[slot] : 0.f;  // composite weight of the sample (PQ)
+  // a pad entry of the nonzero-tile list (every weight of the tile +-0): the tile's y rows are 0,
+  // as mli_live_tiles left them
+  const bool pad = PQ && a.wtile_list && __ballot((__builtin_bit_cast(uint32_t, wgt) & 0x7fffffffu) != 0) == 0;
 
   Ring rg;
   ring_start(rg, a.wfwd, 8 + a.n_heads * 33, bytes);
@@ -705,7 +725,7 @@ MLI_FI void rgb_fwd_body(const mli_rgb_fwd_args& a, uint8_t* lds) {
         for (int i = 0; i < 3; ++i)
           if (i < no) {
             const float y = sigmoidf_acc(acc[i]);
-            gstore_f32(a.y + 8 * slot + off + i, y);
+            gstore_f32(a.y + 8 * slot + off + i, pad ? 0.f : y);
             if (PQ) gq[i] = Q4_SCALE * wgt * (y * (1.0f - y));
           }
       }
@@ -739,7 +759,8 @@ __global__ __launch_bounds__(GFwd::THREADS) void rgb_fwd_kernel(mli_rgb_fwd_args
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   typedef typename std::conditional<TRAIN, GFwdT, GFwd>::type G;
   // live rays: a workgroup past the live tiles returns before any DMA or barrier
-  if (PQ && a.n_live_tiles && (int)(blockIdx.x * G::NW) >= *a.n_live_tiles) return;
+  // (nonzero tiles: past the padded list)
+  if (PQ && a.n_live_tiles && (int)(blockIdx.x * G::NW) >= *(a.wtile_list ? a.n_wtiles_pad : a.n_live_tiles)) return;
   if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= G::NW / 2) rgb_fwd_body<G, TRAIN, PQ, STORE>(a, lds);
   else rgb_fwd_body<G, TRAIN, PQ, DMA>(a, lds);
 }
@@ -758,25 +779,28 @@ MLI_FI void rgb_bwd_body(const mli_rgb_bwd_args& a, uint8_t* lds) {
   const int S = a.R * a.N;
   const int tiles = S / 32;
   // (tile: the position in the masks / dZ images; tile_o: the original tile, for dz4 -- as
-  // rgb_fwd_body)
-  const int tile = blockIdx.x * G::NW + wave;
+  // rgb_fwd_body, the nonzero-tile list included)
+  const int tile = heads_tile<G>(a.wtile_list, wave);
   const int tile_o = a.tile_list ? __builtin_amdgcn_readfirstlane(a.tile_list[tile]) : tile;
   const int m = tile_o * 32 + c;
   const int r = m / a.N, k = m - r * a.N;
   const size_t slot = (size_t)k * a.R + r;
   auto bytes = [](int cc) MLI_LAMBDA_FI { return bwd_bytes(cc); };
-  // ReLU-mask block of global layer L (= head*4 + li, li = 0..3 runs masks 3, 2, 1, 0): the
-  // workgroup's NW tiles are contiguous (NW KiB), DMA'd by the DMA waves (two 16 B per thread)
-  // into mask slot L&1
+  // ReLU-mask block of global layer L (= head*4 + li, li = 0..3 runs masks 3, 2, 1, 0): one KiB per
+  // tile, DMA'd by the DMA waves (two 16 B per thread) into mask slot L&1.  Op u of wave w fetches
+  // the block of the workgroup's wave u ND + w, from that wave's image position mtile[u] (the
+  // positions of a workgroup are consecutive only without the nonzero-tile list)
   constexpr int MASK_OPS = ROLE == DMA ? 2 : ROLE == ALL ? 1 : 0;
+  int mtile[MASK_OPS > 0 ? MASK_OPS : 1];
+#pragma unroll
+  for (int u = 0; u < MASK_OPS; ++u) mtile[u] = heads_tile<G>(a.wtile_list, u * G::ND + wave);
   auto mask_dma = [&](int L) MLI_LAMBDA_FI {
     const int Lc = min(L, 11);
     const int hd = Lc >> 2, ml = 3 - (Lc & 3);
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(a.masks) +
-                         (((size_t)(hd * 4 + ml) * tiles + (size_t)blockIdx.x * G::NW) * 64) * 16;
 #pragma unroll
     for (int u = 0; u < MASK_OPS; ++u)
-      glds16(src + u * (G::MASKB / 2) + threadIdx.x * 16,
+      glds16(reinterpret_cast<const uint8_t*>(a.masks) +
+                 (((size_t)(hd * 4 + ml) * tiles + (size_t)mtile[u]) * 64 + lane) * 16,
              lds + G::MASK_OFF + (L & 1) * G::MASKB + u * (G::MASKB / 2) + wave * 1024);
   };
 

@@ -14,6 +14,9 @@ extern "C" int mli_rgb_fwd(const mli_rgb_fwd_args* a, mli_stream_t s) {
   // live rays: PQ mode only, both arrays or none, a workgroup holds whole rays
   if ((a->tile_list != nullptr) != (a->n_live_tiles != nullptr)) return (int)hipErrorInvalidValue;
   if (a->tile_list && (!pq || 256 % a->N != 0)) return (int)hipErrorInvalidValue;
+  // nonzero tiles: both arrays or none, with the live rays only
+  if ((a->wtile_list != nullptr) != (a->n_wtiles_pad != nullptr)) return (int)hipErrorInvalidValue;
+  if (a->wtile_list && !a->tile_list) return (int)hipErrorInvalidValue;
   const dim3 grid(S / GFwd::SAMPLES), block(GFwd::THREADS);
   if (pq) return mli_launch_rgb_fwd_pq(a, (hipStream_t)s);
   if (train) return mli_launch_rgb_fwd_train(a, (hipStream_t)s);
@@ -32,7 +35,8 @@ extern "C" int mli_rgb_fwd_workspace(const mli_rgb_fwd_args* a, int64_t* bytes) 
   bytes[2] = 0;                                           // (x0T: gone, ABI 15)
   bytes[3] = (int64_t)a->n_heads * (pq ? 3 : 4) * 256 * S * 2;  // xT (training)
   bytes[4] = (int64_t)a->n_heads * 4 * (S / 32) * 64 * 16;  // masks (training)
-  bytes[5] = pq ? (S / 256) * MLI_Q4_SEGS(a->N) * a->n_heads * 257 * 4 * 4 : 0;  // q4 (PQ)
+  // q4 (PQ); wtile_list requested (any non-NULL value): one item per 32-sample tile
+  bytes[5] = pq ? (a->wtile_list ? S / 32 : (S / 256) * MLI_Q4_SEGS(a->N)) * a->n_heads * 257 * 4 * 4 : 0;
   return 0;
 }
 

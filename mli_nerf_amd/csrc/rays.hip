@@ -1056,7 +1056,15 @@ MLI_FI void live_tiles_scan(const mli_live_tiles_args& a) {
           a.tile_list[pos * T + i] = r * T + i;
           a.tile_rank[r * T + i] = before * T + (f != 0 ? i : 0);
           a.wtile_rank[pos * T + i] = f != 0 ? below : W;
-          if ((f >> i) & 1u) a.wtile_list[below] = pos * T + i;
+          if ((f >> i) & 1u) {
+            a.wtile_list[below] = pos * T + i;
+          } else if (a.n_wtiles_pad != nullptr) {
+            // the pads of the heads' last workgroup: the first (-W mod 8) all-zero tiles in compact
+            // order.  All-zero tiles below this one: its position less the nonzero ones below it
+            // (`below` inside a live ray; every one of the W for a dead ray, which follows them all)
+            const int z = pos * T + i - (f != 0 ? below : W);
+            if (z < ((8 - (W & 7)) & 7)) a.wtile_list[W + z] = pos * T + i;
+          }
         }
       },
       L, W);
@@ -1064,6 +1072,7 @@ MLI_FI void live_tiles_scan(const mli_live_tiles_args& a) {
     a.tile_rank[R * T] = L * T;
     a.wtile_rank[R * T] = W;
     a.n_live_tiles[0] = (L + G - 1) / G * G * T;
+    if (a.n_wtiles_pad != nullptr) a.n_wtiles_pad[0] = (W + 7) & ~7;
   }
 }
 
@@ -1089,12 +1098,14 @@ __global__ __launch_bounds__(LR_SCAN) void live_tiles_kernel(mli_live_tiles_args
     for (int j = 0; j < L * CE / 32; ++j)
       if (j * 32 < N && ((seg >> (j * (32 / CE))) & ((1u << (32 / CE)) - 1u)) != 0) f |= 1u << j;
     if (sub == 0) a.flags[r] = (int)f;
-    if (f == 0 && a.y != nullptr) {
+    // the y rows the heads will not write: a dead ray's, and (n_wtiles_pad: the heads take the
+    // nonzero tiles only) those of the all-zero tiles of a live ray
+    if (a.y != nullptr && (f == 0 || a.n_wtiles_pad != nullptr)) {
       const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int e = 0; e < CE; ++e) {
         const int k = CE * sub + e;
-        if (k < N) {
+        if (k < N && ((f >> (k >> 5)) & 1u) == 0) {
           f32x4* row = reinterpret_cast<f32x4*>(a.y + ((size_t)k * R + r) * 8);
           row[0] = z;
           row[1] = z;

@@ -832,14 +832,35 @@ __global__ __launch_bounds__(256) void dw4_partial_kernel(mli_dw4_args a) {
       if (a.tile_rank != nullptr && a.tile_rank[(r0 + sg + 1) * (N / 32)] == a.tile_rank[(r0 + sg) * (N / 32)]) continue;
       const float* d = a.dray + 8 * (r0 + sg);
       const f32x4* q = reinterpret_cast<const f32x4*>(a.q4) + ((size_t)g * segs + sg) * nh * 257;
+      // nonzero tiles: the ray's Q is not in q4; it is 0 plus the items of its nonzero tiles, the
+      // entries [i0, i1) of the list, in ascending order (the forward's sum over the ray's waves
+      // without the +-0 terms)
+      int i0 = 0, i1 = 0;
+      if (a.wtile_rank != nullptr) {
+        const int p0 = a.tile_rank[(r0 + sg) * (N / 32)];
+        i0 = a.wtile_rank[p0];
+        i1 = a.wtile_rank[p0 + N / 32];
+        q = reinterpret_cast<const f32x4*>(a.q4);
+      }
 #pragma unroll
       for (int h = 0; h < 3; ++h) {
         if (h >= nh) break;
         f32x4 dv;
 #pragma unroll
         for (int c = 0; c < 4; ++c) dv[c] = c < a.k_out[h] ? d[3 * h + c] : 0.f;
-        acc[h] += dv * __builtin_nontemporal_load(q + h * 257 + f);
-        if (f == 0) accb[h] += dv * __builtin_nontemporal_load(q + h * 257 + 256);
+        if (a.wtile_rank == nullptr) {
+          acc[h] += dv * __builtin_nontemporal_load(q + h * 257 + f);
+          if (f == 0) accb[h] += dv * __builtin_nontemporal_load(q + h * 257 + 256);
+          continue;
+        }
+        f32x4 v = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
+        for (int i = i0; i < i1; ++i) {
+          const f32x4* qi = q + ((size_t)i * nh + h) * 257;
+          v += __builtin_nontemporal_load(qi + f);
+          if (f == 0) vb += __builtin_nontemporal_load(qi + 256);
+        }
+        acc[h] += dv * v;
+        if (f == 0) accb[h] += dv * vb;
       }
     }
   }
@@ -1093,6 +1114,7 @@ static int dw4_slices(const mli_dw4_args* a) { return std::min(DW4_SLICES, a->R 
 extern "C" int mli_dw4(const mli_dw4_args* a, mli_stream_t s) {
   if (!dw4_valid(a) || !a->q4 || !a->dray || !a->workspace) return (int)hipErrorInvalidValue;
   if (a->tile_rank && 256 % a->N != 0) return (int)hipErrorInvalidValue;
+  if (a->wtile_rank && !a->tile_rank) return (int)hipErrorInvalidValue;  // per-tile items: live rays only
   for (int h = 0; h < a->n_heads; ++h)
     if (!a->dw[h] || !a->db[h]) return (int)hipErrorInvalidValue;
   const int slices = dw4_slices(a);

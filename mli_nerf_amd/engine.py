@@ -164,6 +164,15 @@ SWITCHES = (
     # off.  MLI_ELIDE_OUTSIDE_SAMPLING=0: the dense sampler
     ("elide_outside_sampling", "MLI_ELIDE_OUTSIDE_SAMPLING", True, bool),
 )
+# ... continued (rows of the same form, read and overridden the same way):
+MORE_SWITCHES = (
+    # with skip_zero_tiles: the heads and their backward take the nonzero tiles too, eight to a
+    # workgroup (mli_rgb_fwd_args.wtile_list; q4 then holds one item per nonzero tile and mli_dw4
+    # forms the per-ray sums), equal up to the sign of a zero.  No effect with
+    # skip_zero_tiles off: the dW kernels then stream every live tile, so the heads must write
+    # every live tile.  MLI_SKIP_ZERO_TILES_HEADS=0: every tile of the live rays (A/B runs)
+    ("skip_zero_tiles_heads", "MLI_SKIP_ZERO_TILES_HEADS", True, bool),
+)
 
 
 # stage-b weight-gradient classes in launch order and the head layers each one completes
@@ -225,7 +234,7 @@ class RenderEngine(_Lanes):
         # fixed-order reductions instead of fp32 atomics in mli_wgrad / mli_hash_bwd:
         # bit-reproducible gradients at the cost of partial-slab traffic
         self.deterministic = False
-        for name, env, default, kind in SWITCHES:
+        for name, env, default, kind in SWITCHES + MORE_SWITCHES:
             v = os.environ.get(env)
             setattr(self, name, default if v is None else int(v) if kind is int else v != "0")
         # stage-b training: the output layers' dW from per-tile partials the heads forward forms
@@ -496,7 +505,7 @@ class RenderEngine(_Lanes):
         # the x0 image: SDF feature (k-steps 0..15 of each 32-sample tile) + in training the extras
         # (16..18); the WIDE dW operand (ABI 15)
         feat = self._buf("feat", (S * layout.K0,), torch.float16)
-        xT = masks = w = tl = tr = nl = wl = wr = None
+        xT = masks = w = tl = tr = nl = wl = wr = npad = None
         pq = s_var is not None and self.pq_mode(N, training)
         if training and self.stage == "b" and not self.deterministic:
             # the split-K dW accumulators of this lane's backward: left zero by the last
@@ -508,22 +517,27 @@ class RenderEngine(_Lanes):
             xT = self._buf("xT", (nh, 3 if pq else 4, S * 256), torch.float16)  # ACC frag images
             masks = self._buf("masks", (nh, 4, S // 32, 64, 4), torch.int32)
         if pq and elide and self.elides(N, training):
-            w, tl, tr, nl, wl, wr = self._live_lists(rays, dists, fld, y, s_var, progress)
+            w, tl, tr, nl, wl, wr, npad = self._live_lists(rays, dists, fld, y, s_var, progress)
         else:
             self.densify((rays, dists, fld))  # every ray's h0 tiles are read
             if pq:
                 w = self.weights(rays, dists, fld, s_var, progress)
-        q4 = self._buf("q4", (S // 256, layout.q4_segs(N), nh, 257, 4)) if pq else None
+        # (the heads on the nonzero tiles: one q4 item per tile -- a step buffer, so the prefetch
+        # lanes share the one allocation)
+        q4 = None if not pq else (self._buf("q4", (S // 256, layout.q4_segs(N), nh, 257, 4)) if npad is None
+                                  else self._buf("q4", (S // 32, nh, 257, 4)))
         L.call("mli_rgb_fwd", L.RgbFwdArgs(R, N, L.ptr(rays["center"]), L.ptr(rays["ray_unit"]),
                                            L.ptr(rays["pts_light"]), L.ptr(dists), L.ptr(fld["grad"]),
                                            L.ptr(fld["h0"]), L.ptr(self.wfwd), L.ptr(y), L.ptr(feat),
-                                           L.ptr(xT), L.ptr(masks), nh, L.ptr(w), L.ptr(q4), L.ptr(tl), L.ptr(nl)))
+                                           L.ptr(xT), L.ptr(masks), nh, L.ptr(w), L.ptr(q4), L.ptr(tl), L.ptr(nl),
+                                           L.ptr(wl if npad is not None else None), L.ptr(npad)))
         return dict(y=y, x0T=feat if training else None, xT=xT, masks=masks, feat=feat, q4=q4,
-                    tile_list=tl, tile_rank=tr, n_live_tiles=nl, wtile_list=wl, wtile_rank=wr)
+                    tile_list=tl, tile_rank=tr, n_live_tiles=nl, wtile_list=wl, wtile_rank=wr, n_wtiles_pad=npad)
 
     def _live_lists(self, rays, dists, fld, y, s_var, progress):
         """The composite weights and the live lists of heads(elide=True), the way live_tiles_pass
-        says -> (weights, tile_list, tile_rank, n_live_tiles, wtile_list, wtile_rank).  (Device
+        says -> (weights, tile_list, tile_rank, n_live_tiles, wtile_list, wtile_rank, n_wtiles_pad);
+        n_wtiles_pad is not None when the heads take the nonzero tiles (skip_zero_tiles_heads).  (Device
         side: the grids stay S / 256 and the workgroups past the live tiles return at once.)"""
         N, R = dists.shape
         T = N * R // 32
@@ -535,7 +549,7 @@ class RenderEngine(_Lanes):
             w = self.weights(rays, dists, fld, s_var, progress)
             L.call("mli_live_rays", L.LiveRaysArgs(R, N, L.ptr(w), L.ptr(y), L.ptr(flags), L.ptr(tl), L.ptr(tr),
                                                    L.ptr(nl)))
-            return w, tl, tr, nl, None, None
+            return w, tl, tr, nl, None, None, None
         # the weights, the live rays and the nonzero tiles in one pass
         out = self._composite_out(dists, outputs=False)
         w, comp = out["weights"], self._composite_args(rays, dists, fld, dict(y=None), s_var, progress, out)
@@ -544,10 +558,13 @@ class RenderEngine(_Lanes):
         step = self._lane.step
         if "live_ticket" not in step:   # zeroed once: the pass leaves it zero
             step["live_ticket"] = torch.zeros(1, dtype=torch.int32, device=self.device)
+        npad = None
+        if self.skip_zero_tiles and self.skip_zero_tiles_heads:
+            npad = self._buf("n_wtiles_pad", (1,), torch.int32)
         L.call("mli_live_tiles", L.LiveTilesArgs(comp, L.ptr(y), L.ptr(flags), L.ptr(tl), L.ptr(tr), L.ptr(nl),
                                                  L.ptr(wl), L.ptr(wr), L.ptr(step["live_ticket"]),
-                                                 0 if self.live_tiles_pass == 2 else 1))
-        return (w, tl, tr, nl, wl, wr) if self.skip_zero_tiles else (w, tl, tr, nl, None, None)
+                                                 0 if self.live_tiles_pass == 2 else 1, L.ptr(npad)))
+        return (w, tl, tr, nl, wl, wr, npad) if self.skip_zero_tiles else (w, tl, tr, nl, None, None, None)
 
     def _composite_out(self, dists, outputs=True, extras=False):
         """The composite kernels' outputs: the weights buffer, fresh rgb ... (``extras``: + inference maps)."""
@@ -861,7 +878,9 @@ class RenderEngine(_Lanes):
         dzT = self._buf("dzT", (3, 4, S * 256), torch.float16)  # ACC frag images
         L.call("mli_rgb_bwd", L.RgbBwdArgs(R, N, L.ptr(dz4), L.ptr(self.wbwd), L.ptr(hd["masks"]), L.ptr(dzT),
                                            L.ptr(dz4T), 1 if rebuild else 0, L.ptr(hd.get("tile_list")),
-                                           L.ptr(hd.get("n_live_tiles"))))
+                                           L.ptr(hd.get("n_live_tiles")),
+                                           L.ptr(hd.get("wtile_list") if hd.get("n_wtiles_pad") is not None else None),
+                                           L.ptr(hd.get("n_wtiles_pad"))))
         jobs, ad, (dw4, db4, k4) = self._wgrad_plan(dzT, dz4T, hd, dwbuf, flat, grad_out, S,
                                                     (dz4, R, N) if rebuild else None)
         if self.gate_wgrad:  # Trainer.prefetch(gate="wgrad"): next geometry may start here
@@ -906,7 +925,8 @@ class RenderEngine(_Lanes):
         """PQ mode: the output layers' dW / db from the forward's q4 and the per-ray D."""
         args = L.Dw4Args(R, N, 3, L.ptr(hd["q4"]), L.ptr(self._lane.step["dray"]), scale / L.Q4_SCALE,
                          (C.c_void_p * 3)(*dw4), (C.c_void_p * 3)(*db4), (C.c_int * 3)(*k4), None,
-                         L.ptr(hd.get("tile_rank")))
+                         L.ptr(hd.get("tile_rank")),
+                         L.ptr(hd.get("wtile_rank") if hd.get("n_wtiles_pad") is not None else None))
         args.workspace = L.ptr(self._buf("dw4_ws", (L.workspace("mli_dw4", args)[0] // 4,)))
         L.call("mli_dw4", args)
 
