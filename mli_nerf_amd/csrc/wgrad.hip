@@ -747,6 +747,17 @@ struct RArgs {
   int n_jobs, n_split;
 };
 
+// acc += slices sp .. sp + B - 1 in that order, the B loads issued before the first add
+template <int B>
+__device__ __forceinline__ void reduce_batch(const float* p, int64_t stride, int& sp, float& acc) {
+  float v[B];
+#pragma unroll
+  for (int q = 0; q < B; ++q) v[q] = p[(int64_t)(sp + q) * stride];
+#pragma unroll
+  for (int q = 0; q < B; ++q) acc += v[q];
+  sp += B;
+}
+
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(RArgs r) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= r.first[r.n_jobs]) return;
@@ -761,16 +772,14 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(RArgs r) {
   // 16 slices' loads in flight, summed in slice order (the same fixed order: bit-identical).
   // The plain loop was one load -> vmcnt(0) -> add per slice: 80 round trips, 150 us for the
   // WIDE slabs beside the prefetched geometry (profiles/r5/final2 trace).
+  // The remainder the same way, in batches of 8 / 4 / 2 / 1 (BIG's 28 slices: 16 + 8 + 4).
   float acc = 0.f;
   int sp = 0;
-  for (; sp + 16 <= r.n_split; sp += 16) {
-    float v[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) v[q] = p[(int64_t)(sp + q) * stride];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc += v[q];
-  }
-  for (; sp < r.n_split; ++sp) acc += p[(int64_t)sp * stride];
+  while (sp + 16 <= r.n_split) reduce_batch<16>(p, stride, sp, acc);
+  if (sp + 8 <= r.n_split) reduce_batch<8>(p, stride, sp, acc);
+  if (sp + 4 <= r.n_split) reduce_batch<4>(p, stride, sp, acc);
+  if (sp + 2 <= r.n_split) reduce_batch<2>(p, stride, sp, acc);
+  if (sp < r.n_split) reduce_batch<1>(p, stride, sp, acc);
   if (loc < MK) {
     const int row = (int)(loc / r.K[j]), col = (int)(loc - (int64_t)row * r.K[j]);
     r.dw[j][(size_t)row * r.ldw[j] + col] = acc;
@@ -811,65 +820,125 @@ __global__ __launch_bounds__(512) void frag_rows_kernel(mli_frag_rows_args a) {
 // ---------------------------------------------------------------------- output layer from Q
 // mli_dw4: dW4[c][f] = scale * sum_(wg,seg) dray[ray][3h + c] * q4[wg][seg][h][f][c] (rows f < 256)
 // and db4 from row 256.  Pass 1: workgroup b sums the (wg, seg) items of workgroups
-// [wg0(b), wg0(b+1)) -- one thread per row f (257 rows: thread 0 also takes row 256) -- into
-// ws[b][h][257][4]; pass 2: one workgroup per (h, row) sums the slices in a fixed order.
+// [wg0(b), wg0(b+1)) -- one thread per row f (257 rows: a fifth wave's first lane takes row 256,
+// which follows row 255 in every item) -- into ws[b][h][257][4]; pass 2: one workgroup per
+// (h, row) sums the slices in a fixed order.
+//
+// Pass 1 streams.  32 workgroups' ray segments at a time, one thread per segment
+// reads its ranks and its dray row once; a scan over the item counts lays the segments' items out
+// as one flat list in LDS (q4 item, and at a ray's last item the segment whose dv it meets).  The
+// rows then walk the list DW4_BATCH items at a time: every load of a batch (x n_heads) is issued
+// before the first add.  The sums are the ones of the plain loop, in its order: per-tile items
+// v = 0 + item_i0 + ... + item_(i1-1), then acc = acc + dv * v, rays ascending; per-ray and dense
+// items acc = acc + dv * item.
 constexpr int DW4_SLICES = 256;
+constexpr int DW4_BATCH = 8;       // items in flight per row: 8 x 3 heads x 16 B x 257 rows = 96 KiB per CU
+constexpr int DW4_CHUNK = 32;      // workgroups per list: 8 segment slots each (MLI_Q4_SEGS <= 8)
+constexpr int DW4_THREADS = 320;   // 257 rows
 
-__global__ __launch_bounds__(256) void dw4_partial_kernel(mli_dw4_args a) {
-  const int N = a.N, nh = a.n_heads, segs = MLI_Q4_SEGS(N);
+template <int NH>
+__global__ __launch_bounds__(DW4_THREADS) void dw4_partial_kernel(mli_dw4_args a) {
+  __shared__ int2 s_item[DW4_CHUNK * 8 * 8];  // (q4 item, segment slot at a ray's last item else -1); <= 8 items per ray
+  __shared__ f32x4 s_dv[DW4_CHUNK * 8][NH];
+  __shared__ int s_wsum[DW4_THREADS / 64];
+  const int N = a.N, segs = MLI_Q4_SEGS(N), T = N / 32;
   const int wgs = a.R * N / 256;
   const int g0 = (int)((int64_t)wgs * blockIdx.x / gridDim.x);
   const int g1 = (int)((int64_t)wgs * (blockIdx.x + 1) / gridDim.x);
-  const int f = threadIdx.x;
-  f32x4 acc[3], accb[3];
+  const int f = threadIdx.x, lane = f & 63, wave = f >> 6;
+  const bool per_tile = a.wtile_rank != nullptr;
+  const char* q = reinterpret_cast<const char*>(a.q4);
+  f32x4 acc[NH], v[NH];
 #pragma unroll
-  for (int h = 0; h < 3; ++h) acc[h] = accb[h] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int g = g0; g < g1; ++g) {
-    const int r0 = g * 256 / N, nseg = (g * 256 + 255) / N - r0 + 1;
-    for (int sg = 0; sg < nseg; ++sg) {
-      // live rays: a ray without a live tile (pad rays too) adds exact zeros and its q4 item was
-      // not written (or, a pad ray's, is all zero): skipped
-      if (a.tile_rank != nullptr && a.tile_rank[(r0 + sg + 1) * (N / 32)] == a.tile_rank[(r0 + sg) * (N / 32)]) continue;
-      const float* d = a.dray + 8 * (r0 + sg);
-      const f32x4* q = reinterpret_cast<const f32x4*>(a.q4) + ((size_t)g * segs + sg) * nh * 257;
-      // nonzero tiles: the ray's Q is not in q4; it is 0 plus the items of its nonzero tiles, the
-      // entries [i0, i1) of the list, in ascending order (the forward's sum over the ray's waves
-      // without the +-0 terms)
-      int i0 = 0, i1 = 0;
-      if (a.wtile_rank != nullptr) {
-        const int p0 = a.tile_rank[(r0 + sg) * (N / 32)];
-        i0 = a.wtile_rank[p0];
-        i1 = a.wtile_rank[p0 + N / 32];
-        q = reinterpret_cast<const f32x4*>(a.q4);
-      }
-#pragma unroll
-      for (int h = 0; h < 3; ++h) {
-        if (h >= nh) break;
-        f32x4 dv;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) dv[c] = c < a.k_out[h] ? d[3 * h + c] : 0.f;
-        if (a.wtile_rank == nullptr) {
-          acc[h] += dv * __builtin_nontemporal_load(q + h * 257 + f);
-          if (f == 0) accb[h] += dv * __builtin_nontemporal_load(q + h * 257 + 256);
-          continue;
+  for (int h = 0; h < NH; ++h) acc[h] = v[h] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int gc = g0; gc < g1; gc += DW4_CHUNK) {
+    // segment slot f: workgroup gc + f / 8, segment f % 8; its items [start, start + n)
+    int n = 0, start = 0;
+    const int g = gc + (f >> 3), sg = f & 7;
+    if (f < DW4_CHUNK * 8 && g < g1) {
+      const int r0 = g * 256 / N, nseg = (g * 256 + 255) / N - r0 + 1;
+      if (sg < nseg) {
+        const int ray = r0 + sg;
+        start = g * segs + sg;
+        n = 1;
+        if (a.tile_rank != nullptr) {
+          // live rays: a ray without a live tile (pad rays too) adds exact zeros and its q4 item
+          // was not written (or, a pad ray's, is all zero): skipped
+          const int p0 = a.tile_rank[ray * T];
+          if (a.tile_rank[(ray + 1) * T] == p0) {
+            n = 0;
+          } else if (per_tile) {
+            // nonzero tiles: the ray's Q is not in q4; it is 0 plus the items of its nonzero
+            // tiles, the entries [i0, i1) of the list, in ascending order (the forward's sum over
+            // the ray's waves without the +-0 terms)
+            start = a.wtile_rank[p0];
+            n = min(max(a.wtile_rank[p0 + T] - start, 0), T);
+          }
         }
-        f32x4 v = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
-        for (int i = i0; i < i1; ++i) {
-          const f32x4* qi = q + ((size_t)i * nh + h) * 257;
-          v += __builtin_nontemporal_load(qi + f);
-          if (f == 0) vb += __builtin_nontemporal_load(qi + 256);
+        if (n > 0) {
+          const float* d = a.dray + 8 * ray;
+#pragma unroll
+          for (int h = 0; h < NH; ++h) {
+            f32x4 dv;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) dv[c] = c < a.k_out[h] ? d[3 * h + c] : 0.f;
+            s_dv[f][h] = dv;
+          }
         }
-        acc[h] += dv * v;
-        if (f == 0) accb[h] += dv * vb;
       }
     }
-  }
-  f32x4* ws = reinterpret_cast<f32x4*>(a.workspace) + (size_t)blockIdx.x * nh * 257;
+    int incl = n;
 #pragma unroll
-  for (int h = 0; h < 3; ++h) {
-    if (h >= nh) break;
-    ws[h * 257 + f] = acc[h];
-    if (f == 0) ws[h * 257 + 256] = accb[h];
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(incl, o);
+      if (lane >= o) incl += t;
+    }
+    if (lane == 63) s_wsum[wave] = incl;
+    __syncthreads();
+    int pos = incl - n, total = 0;
+#pragma unroll
+    for (int w = 0; w < DW4_THREADS / 64; ++w) {
+      const int t = s_wsum[w];
+      if (w < wave) pos += t;
+      total += t;
+    }
+    total = __builtin_amdgcn_readfirstlane(total);
+    for (int i = 0; i < n; ++i) s_item[pos + i] = int2{start + i, i == n - 1 ? f : -1};
+    __syncthreads();
+    if (f < 257) {
+      for (int k0 = 0; k0 < total; k0 += DW4_BATCH) {
+        f32x4 x[DW4_BATCH][NH];
+        int end[DW4_BATCH];
+#pragma unroll
+        for (int j = 0; j < DW4_BATCH; ++j) {
+          if (k0 + j >= total) break;
+          const int2 it = s_item[k0 + j];
+          end[j] = __builtin_amdgcn_readfirstlane(it.y);
+          const char* qi = q + (size_t)__builtin_amdgcn_readfirstlane(it.x) * (NH * 257 * 16);
+#pragma unroll
+          for (int h = 0; h < NH; ++h)
+            x[j][h] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(qi + (unsigned)(h * 257 + f) * 16u));
+        }
+#pragma unroll
+        for (int j = 0; j < DW4_BATCH; ++j) {
+          if (k0 + j >= total) break;
+#pragma unroll
+          for (int h = 0; h < NH; ++h) {
+            v[h] = per_tile ? v[h] + x[j][h] : x[j][h];
+            if (end[j] >= 0) {
+              acc[h] = acc[h] + s_dv[end[j]][h] * v[h];
+              v[h] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();  // the lists are rewritten by the next chunk
+  }
+  if (f < 257) {
+    f32x4* ws = reinterpret_cast<f32x4*>(a.workspace) + (size_t)blockIdx.x * NH * 257;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) ws[h * 257 + f] = acc[h];
   }
 }
 
@@ -1118,7 +1187,9 @@ extern "C" int mli_dw4(const mli_dw4_args* a, mli_stream_t s) {
   for (int h = 0; h < a->n_heads; ++h)
     if (!a->dw[h] || !a->db[h]) return (int)hipErrorInvalidValue;
   const int slices = dw4_slices(a);
-  hipLaunchKernelGGL(dw4_partial_kernel, dim3(slices), dim3(256), 0, (hipStream_t)s, *a);
+  if (a->n_heads == 3) hipLaunchKernelGGL(dw4_partial_kernel<3>, dim3(slices), dim3(DW4_THREADS), 0, (hipStream_t)s, *a);
+  else if (a->n_heads == 2) hipLaunchKernelGGL(dw4_partial_kernel<2>, dim3(slices), dim3(DW4_THREADS), 0, (hipStream_t)s, *a);
+  else hipLaunchKernelGGL(dw4_partial_kernel<1>, dim3(slices), dim3(DW4_THREADS), 0, (hipStream_t)s, *a);
   hipLaunchKernelGGL(dw4_reduce_kernel, dim3(a->n_heads * 257), dim3(256), 0, (hipStream_t)s, *a, slices);
   MLI_LAUNCH_CHECK();
 }
