@@ -358,6 +358,30 @@ RELIGHT_ENTRY_POINTS = {"mli_light_points": LightPointsArgs, "mli_camera_hit": C
                         "mli_light_shadows": LightShadowsArgs}
 RELIGHT_WORKSPACE = {}
 
+# ---------------------------------------------------------------- include/mli_lpips.h
+class LpipsPackArgs(C.Structure):
+    _fields_ = [("w", P * 5), ("b", P * 5), ("lin", P * 5), ("shift", P), ("scale", P), ("packed", P)]
+
+
+class LpipsArgs(C.Structure):
+    _fields_ = [("B", I32), ("H", I32), ("W", I32), ("normalize", I32), ("pred_f32", P), ("pred_u8", P),
+                ("target_f32", P), ("target_u8", P), ("packed", P), ("lpips", P), ("layers", P), ("taps", P * 6),
+                ("scratch", P)]
+
+
+LPIPS_ABI_VERSION = 1        # include/mli_lpips.h MLI_LPIPS_ABI_VERSION
+LPIPS_MIN_SIDE = 31          # MLI_LPIPS_MIN_SIDE
+LPIPS_MAX_SIDE = 4096        # MLI_LPIPS_MAX_SIDE
+LPIPS_MAX_PAIRS = 64         # MLI_LPIPS_MAX_PAIRS
+LPIPS_LAYERS = 5             # MLI_LPIPS_LAYERS
+LPIPS_TILE = (64, 64, 16)    # MLI_LPIPS_TILE_M, MLI_LPIPS_TILE_N, MLI_LPIPS_TILE_K
+LPIPS_K1_PADDED = 368        # MLI_LPIPS_K1_PADDED
+LPIPS_DIST_PIXELS = 16       # MLI_LPIPS_DIST_PIXELS
+
+# the LPIPS op, versioned apart from the ABIs above
+LPIPS_ENTRY_POINTS = {"mli_lpips_pack": LpipsPackArgs, "mli_lpips": LpipsArgs}
+LPIPS_WORKSPACE = {"mli_lpips_pack": 1, "mli_lpips": 1}
+
 _lib = None
 
 
@@ -370,13 +394,14 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         for name, st in list(ENTRY_POINTS.items()) + list(MESH_ENTRY_POINTS.items()) + list(
                 LABELS_ENTRY_POINTS.items()) + list(MESH_CC_ENTRY_POINTS.items()) + list(
-                METRICS_ENTRY_POINTS.items()) + list(RELIGHT_ENTRY_POINTS.items()):
+                METRICS_ENTRY_POINTS.items()) + list(RELIGHT_ENTRY_POINTS.items()) + list(
+                LPIPS_ENTRY_POINTS.items()):
             fn = getattr(_lib, name)
             fn.argtypes = [C.POINTER(st), P]
             fn.restype = I32
         for table, points in ((WORKSPACE, ENTRY_POINTS), (MESH_WORKSPACE, MESH_ENTRY_POINTS),
                               (LABELS_WORKSPACE, LABELS_ENTRY_POINTS), (MESH_CC_WORKSPACE, MESH_CC_ENTRY_POINTS),
-                              (METRICS_WORKSPACE, METRICS_ENTRY_POINTS)):
+                              (METRICS_WORKSPACE, METRICS_ENTRY_POINTS), (LPIPS_WORKSPACE, LPIPS_ENTRY_POINTS)):
             for name in table:
                 fn = getattr(_lib, name + "_workspace")
                 fn.argtypes = [C.POINTER(points[name]), C.POINTER(I64)]
@@ -386,6 +411,7 @@ def lib():
         _lib.mli_mesh_cc_abi_version.restype = I32
         _lib.mli_metrics_abi_version.restype = I32
         _lib.mli_relight_abi_version.restype = I32
+        _lib.mli_lpips_abi_version.restype = I32
         _lib.mli_abi_version.restype = I32
         _lib.mli_error_string.restype = C.c_char_p
         _lib.mli_error_string.argtypes = [I32]
@@ -394,7 +420,8 @@ def lib():
                 or _lib.mli_labels_abi_version() != LABELS_ABI_VERSION
                 or _lib.mli_mesh_cc_abi_version() != MESH_CC_ABI_VERSION
                 or _lib.mli_metrics_abi_version() != METRICS_ABI_VERSION
-                or _lib.mli_relight_abi_version() != RELIGHT_ABI_VERSION):
+                or _lib.mli_relight_abi_version() != RELIGHT_ABI_VERSION
+                or _lib.mli_lpips_abi_version() != LPIPS_ABI_VERSION):
             raise ImportError("libmli_hip.so ABI mismatch")
         from . import build as _build
         # in-tree sources: the in-tree library must match them.  Only a library OUTSIDE the in-tree
@@ -428,7 +455,8 @@ def workspace(name, args):
     if rc != 0:
         raise RuntimeError("%s_workspace failed: %s (%d)" % (name, lib().mli_error_string(rc).decode(), rc))
     return [int(out[i]) for i in range(WORKSPACE.get(name) or MESH_WORKSPACE.get(name) or LABELS_WORKSPACE.get(name)
-                                         or MESH_CC_WORKSPACE.get(name) or METRICS_WORKSPACE[name])]
+                                         or MESH_CC_WORKSPACE.get(name) or METRICS_WORKSPACE.get(name)
+                                         or LPIPS_WORKSPACE[name])]
 
 
 def ptr(t):

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmli_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["rays.hip", "sdf.hip", "mlp_fwd.hip", "mlp_fwd_pq.hip", "mlp_fwd_train.hip", "mlp_bwd.hip", "mlp_geo.hip",
-           "wgrad.hip", "params.hip", "loss.hip", "mesh.hip", "labels.hip", "mesh_cc.hip", "metrics.hip"]
+           "wgrad.hip", "params.hip", "loss.hip", "mesh.hip", "labels.hip", "mesh_cc.hip", "metrics.hip", "lpips.hip"]
 # sdf.hip: no SLP packing, so fma(fp16 -> fp32 feature, w, acc) selects v_fma_mix_f32 (one
 # instruction) instead of v_cvt_f32_f16 x2 + v_pk_fma_f32
 # No SLP packing of scalar fp32 math in the MFMA and geometry kernels: v_pk_*_f32 beside MFMAs
@@ -19,7 +19,7 @@ SOURCES = ["rays.hip", "sdf.hip", "mlp_fwd.hip", "mlp_fwd_pq.hip", "mlp_fwd_trai
 # its even-aligned register pairs raise the VGPR count (field_mlp 167 -> 118).
 # rays.hip / params.hip (VALU-only sampling, AdamW) keep it.
 PER_FILE = {s: ["-fno-slp-vectorize"] for s in ("sdf.hip", "mlp_fwd.hip", "mlp_fwd_pq.hip", "mlp_fwd_train.hip",
-                                                 "mlp_bwd.hip", "mlp_geo.hip", "wgrad.hip", "loss.hip")}
+                                                 "mlp_bwd.hip", "mlp_geo.hip", "wgrad.hip", "loss.hip", "lpips.hip")}
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-I", os.path.join(REPO, "include"), "-I", CSRC]
 # the device assembly of every file stays next to its object (-save-temps=obj), so that build()
@@ -35,7 +35,8 @@ def _deps():
         os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [
         os.path.join(REPO, "include", "mli_hip.h"), os.path.join(REPO, "include", "mli_mesh.h"),
         os.path.join(REPO, "include", "mli_labels.h"), os.path.join(REPO, "include", "mli_mesh_cc.h"),
-        os.path.join(REPO, "include", "mli_metrics.h"), os.path.join(REPO, "include", "mli_relight.h")]
+        os.path.join(REPO, "include", "mli_metrics.h"), os.path.join(REPO, "include", "mli_relight.h"),
+        os.path.join(REPO, "include", "mli_lpips.h")]
 
 
 def source_hash():

@@ -13,8 +13,9 @@ of libmli_hip.so behind include/mli_metrics.h:
   ``data["image"]`` on the device, both quantised as ``relight.save_image`` writes them;
 * ``python -m mli_nerf_amd.metrics`` is the command line.
 
-LPIPS is not built (``compare_image_lists`` takes an ``lpips_fn``); pairs of different size raise.
-DESIGN.md §17 has the definitions.  There is no CPU path: without the library the op raises.
+LPIPS comes from ``mli_nerf_amd.lpips`` when the user names a weight file (``--lpips_weights``, or an
+``lpips.LPIPS`` passed as ``lpips_fn`` / ``lpips``); no weights are shipped.  Pairs of different size
+raise.  DESIGN.md §17 and §20 have the definitions.  There is no CPU path: without the library the op raises.
 """
 import json
 import os
@@ -168,6 +169,12 @@ def _score(items, gamma_corr, mask_pred, device, lpips_fn=None):
     rows = [{"psnr": float(m["psnr"][i]), "ssim": float(m["ssim"][i]), "mse": float(m["mse"][i])}
             for i in range(len(items))]
     if lpips_fn is not None:
+        from .lpips import LPIPS
+        if isinstance(lpips_fn, LPIPS):   # the whole run in one call; a pair's bits do not depend on the batch
+            vals = lpips_fn(m["prepared_pred"].float(), m["prepared_target"].float())
+            for row, v in zip(rows, vals):
+                row["lpips"] = float(v)
+            return rows
         for i, row in enumerate(rows):
             row["lpips"] = float(lpips_fn(m["prepared_pred"][i:i + 1].float(), m["prepared_target"][i:i + 1].float()))
     return rows
@@ -258,12 +265,14 @@ def get_nrhints(path_pred, path_gt):
 
 # ---------------------------------------------------------------------------- a trained model
 @torch.no_grad()
-def evaluate(trainer, data_loader, output_dir=None, mode="test"):
+def evaluate(trainer, data_loader, output_dir=None, mode="test", lpips=None):
     """The loop of ``loop.test_save`` (iteration sys.maxsize in mode 'test', Model.inference per
     frame) with ``rgb_map`` scored against ``data["image"]`` on the device, both quantised as
     ``relight.save_image`` writes them: the numbers of the PNGs, without the PNGs.  Returns
     {'frames': [{'index', 'psnr', 'ssim', 'mse', 'ssim_channels'}], 'mean': {...}} and writes it to
-    ``output_dir``/metrics.json when a directory is given."""
+    ``output_dir``/metrics.json when a directory is given.  With ``lpips`` (an ``lpips.LPIPS``) every
+    frame and the mean also carry 'lpips', of the same quantised planes as float32; frames smaller
+    than 31 x 31 then raise."""
     model = trainer.model
     model.eval()
     c_iter = sys.maxsize if mode == "test" else trainer.current_iteration
@@ -276,15 +285,20 @@ def evaluate(trainer, data_loader, output_dir=None, mode="test"):
             out = model.inference(data)
             if "image" not in data:
                 raise ValueError("evaluate: the loader's frames carry no 'image' to score against")
-            m = image_metrics(out["rgb_map"].detach().float(), data["image"].float(), quantize=True)
+            m = image_metrics(out["rgb_map"].detach().float(), data["image"].float(), quantize=True,
+                              return_prepared=lpips is not None)
+            lp = None if lpips is None else lpips(m["prepared_pred"].float(), m["prepared_target"].float())
             for i in range(m["mse"].numel()):
                 frames.append({"index": len(frames), "psnr": float(m["psnr"][i]), "ssim": float(m["ssim"][i]),
                                "mse": float(m["mse"][i]), "ssim_channels": m["ssim_channels"][i].tolist()})
+                if lp is not None:
+                    frames[-1]["lpips"] = float(lp[i])
     finally:
         trainer.current_iteration = saved
     if not frames:
         raise ValueError("evaluate: the loader gave no frames")
-    result = {"frames": frames, "mean": _mean(frames, ("psnr", "ssim", "mse"))}
+    keys = ("psnr", "ssim", "mse") + (("lpips",) if lpips is not None else ())
+    result = {"frames": frames, "mean": _mean(frames, keys)}
     if output_dir is not None:
         os.makedirs(output_dir, exist_ok=True)
         with open(os.path.join(output_dir, "metrics.json"), "w") as f:
@@ -294,7 +308,10 @@ def evaluate(trainer, data_loader, output_dir=None, mode="test"):
 
 # ---------------------------------------------------------------------------- command line
 def format_result(mean):
-    """The reference's print format without its LPIPS column: psnr .2f, ssim .4f, mse .4f."""
+    """The reference's print format: psnr .2f, ssim .4f, lpips .4f, mse .4f; without an LPIPS mean
+    the line has no such column."""
+    if "lpips" in mean:
+        return "%.2f %.4f %.4f %.4f" % (mean["psnr"], mean["ssim"], mean["lpips"], mean["mse"])
     return "%.2f %.4f %.4f" % (mean["psnr"], mean["ssim"], mean["mse"])
 
 
@@ -312,7 +329,16 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--json", help="also write the means to this file")
+    ap.add_argument("--lpips_weights", nargs="+", metavar="PATH", default=None,
+                    help="add the LPIPS (alex) column: an lpips.LPIPS state dict, or torchvision's alexnet "
+                         "file and lpips's alex.pth")
     args = ap.parse_args(argv)
+    lpips_fn = None
+    if args.lpips_weights is not None:
+        if len(args.lpips_weights) > 2:
+            ap.error("--lpips_weights takes one or two files")
+        from . import lpips as _lpips
+        lpips_fn = _lpips.LPIPS(_lpips.load_weights(*args.lpips_weights), args.device)
     comps = args.components or (list(COMPONENTS) if args.layout == "syn_intrinsic" else ["Img"])
     if args.layout != "syn_intrinsic" and comps != ["Img"]:
         ap.error("--layout %s has the component Img alone" % args.layout)
@@ -331,7 +357,7 @@ def main(argv=None):
             preds, gts = get_nrhints(args.pred, args.gt)
             alphas = [None] * len(gts)
         results[comp] = compare_image_lists(preds, gts, alphas, gamma_corr=comp == "Sha", mask_pred=args.mask_pred,
-                                            batch=args.batch, device=args.device)
+                                            lpips_fn=lpips_fn, batch=args.batch, device=args.device)
         print(comp, format_result(results[comp]))
     if args.json:
         with open(args.json, "w") as f:

@@ -1169,13 +1169,13 @@ class Trainer:
         from . import loop
         return loop.test_save(self, data_loader, output_dir, inference_args, mode, show_pbar)
 
-    def evaluate(self, data_loader, output_dir=None, mode="test"):
+    def evaluate(self, data_loader, output_dir=None, mode="test", lpips=None):
         """The frames of ``test_save`` scored on the device instead of saved: PSNR, SSIM and MSE of
         ``rgb_map`` against the frame's image, per frame and averaged, as
         NeuralLumen/scripts/compute_metrics.py gives them for the saved PNGs (see
-        mli_nerf_amd.metrics)."""
+        mli_nerf_amd.metrics); with ``lpips`` (an ``mli_nerf_amd.lpips.LPIPS``) its LPIPS column too."""
         from . import metrics
-        return metrics.evaluate(self, data_loader, output_dir, mode)
+        return metrics.evaluate(self, data_loader, output_dir, mode, lpips)
 
     def test_images(self, data_loader, output_dir=None, setting_list=None, mode="test", show_pbar=False):
         """projects/nerf/trainers/base.py:218-260 (test.py:122-126)."""
