@@ -181,7 +181,7 @@ int mli_sdf_workspace(const mli_sdf_args* a, int64_t* bytes);
  * finite, nondecreasing in k and inside [near, far]: with sdf = outside_val and zero gradients
  * the composite weights of such a ray are exactly 0 for any such dists.  The rays counted by
  * n_pad get the row too; the listed rounds that follow overwrite it with the dense sampler's. */
-struct mli_inside_list_args_s {
+typedef struct {
   int R, N;
   int n_pad;              /* >= 0 */
   const uint8_t* outside; /* [R] */
@@ -194,8 +194,7 @@ struct mli_inside_list_args_s {
   const float* near_;     /* [R] or NULL */
   const float* far_;      /* [R] or NULL */
   float* dists;           /* [N][R] or NULL */
-};
-typedef struct mli_inside_list_args_s mli_inside_list_args;
+} mli_inside_list_args;
 int mli_inside_list(const mli_inside_list_args* a, mli_stream_t s);
 
 /* ---------------------------------------------------------------- sampling
@@ -470,14 +469,13 @@ int mli_dw4_workspace(const mli_dw4_args* a, int64_t* bytes);
  * and zeroes the y rows of every dead ray (mli_composite_loss reads y of every sample; the pad
  * rays' rows are rewritten by mli_rgb_fwd).  256 % N == 0, R % G == 0.  Two launches: a per-ray
  * flag pass over the weights, then one workgroup's scan over the R flags (no atomics). */
-struct mli_live_rays_args_s {
+typedef struct {
   int R, N;
   const float* weights;   /* [N][R] */
   float* y;               /* [N][R][8] or NULL */
   int32_t* flags;         /* scratch [R] */
   int32_t* tile_list; int32_t* tile_rank; int32_t* n_live_tiles;
-};
-typedef struct mli_live_rays_args_s mli_live_rays_args;
+} mli_live_rays_args;
 int mli_live_rays(const mli_live_rays_args* a, mli_stream_t s);
 
 /* mli_live_tiles: the weights pass (mli_composite_fwd with y = NULL; comp.y must be NULL and the
@@ -499,7 +497,7 @@ int mli_live_rays(const mli_live_rays_args* a, mli_stream_t s);
  * which the caller zeroes once, at allocation; nobody waits for another workgroup.
  * scan_launch != 0: the scan is a second launch of one workgroup and ticket is not used.
  * 256 % N == 0, R % (256 / N) == 0. */
-struct mli_live_tiles_args_s {
+typedef struct {
   mli_composite_args comp; /* as mli_composite_fwd, y == NULL; weights [N][R] is written */
   float* y;                /* [N][R][8] or NULL */
   int32_t* flags;          /* [R] */
@@ -513,8 +511,7 @@ struct mli_live_tiles_args_s {
    * so there are enough), writes W rounded up to a multiple of 8 here, and the pass also zeroes
    * the y rows of the all-zero tiles inside live rays (the heads no longer write them). */
   int32_t* n_wtiles_pad;
-};
-typedef struct mli_live_tiles_args_s mli_live_tiles_args;
+} mli_live_tiles_args;
 int mli_live_tiles(const mli_live_tiles_args* a, mli_stream_t s);
 
 /* ---------------------------------------------------------------- stage a (geometry training)

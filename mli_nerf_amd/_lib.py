@@ -2,6 +2,7 @@
 missing -- there is no CPU fallback on the product path."""
 import ctypes as C
 import os
+from collections import namedtuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # MLI_HIP_LIB selects an experiment build (tools/kbench.py A/B runs); default: the in-tree lib
@@ -87,7 +88,7 @@ class WgradJob(C.Structure):
                 ("rb_cnt", I32), ("rb_R", I32), ("rb_N", I32)]
 
 
-# mli_wgrad_job operand layouts (MLI_WGRAD_LAYOUT_*)
+# mli_wgrad_job operand layouts
 ROWS, TILED, FRAG_ACC, FRAG_NAT = 0, 1, 2, 3
 
 
@@ -120,7 +121,7 @@ class LiveTilesArgs(C.Structure):
                 ("n_wtiles_pad", P)]
 
 
-Q4_SCALE = 65536.0  # include/mli_hip.h MLI_Q4_SCALE
+Q4_SCALE = 65536.0
 
 
 class LossArgs(C.Structure):
@@ -222,7 +223,7 @@ class FragRowsArgs(C.Structure):
                 ("ld", I64), ("col0", I64), ("row0", I32)]
 
 
-ABI_VERSION = 18  # include/mli_hip.h MLI_ABI_VERSION
+ABI_VERSION = 18
 
 ENTRY_POINTS = {
     "mli_rays": RaysArgs, "mli_hashgrid_fwd": HashgridArgs, "mli_sdf": SdfArgs,
@@ -257,8 +258,8 @@ class McArgs(C.Structure):
                 ("vert_keys", P), ("faces", P), ("face_keys", P)]
 
 
-MESH_ABI_VERSION = 1  # include/mli_mesh.h MLI_MESH_ABI_VERSION
-MC_CHUNK = 256        # MLI_MC_CHUNK
+MESH_ABI_VERSION = 1
+MC_CHUNK = 256
 
 # the iso-surface ops, versioned apart from the rendering ABI above (ENTRY_POINTS / WORKSPACE)
 MESH_ENTRY_POINTS = {"mli_mc_count": McArgs, "mli_mc_emit": McArgs}
@@ -288,12 +289,12 @@ class LabelFillArgs(C.Structure):
                 ("donor_feat", P), ("partial", P)]
 
 
-LABELS_ABI_VERSION = 1     # include/mli_labels.h MLI_LABELS_ABI_VERSION
-LABELS_MAX_RADIUS = 15     # MLI_LABELS_MAX_RADIUS
-LABELS_MAX_K = 4           # MLI_LABELS_MAX_K
-LABELS_TILE = (32, 8)      # MLI_LABELS_TILE_X, MLI_LABELS_TILE_Y
-LABELS_DONOR_TILE = 256    # MLI_LABELS_DONOR_TILE
-LABELS_MAX_SLICES = 64     # MLI_LABELS_MAX_SLICES
+LABELS_ABI_VERSION = 1
+LABELS_MAX_RADIUS = 15
+LABELS_MAX_K = 4
+LABELS_TILE = (32, 8)
+LABELS_DONOR_TILE = 256
+LABELS_MAX_SLICES = 64
 
 # the pseudo-label ops, versioned apart from both ABIs above
 LABELS_ENTRY_POINTS = {"mli_label_morph": LabelMorphArgs, "mli_label_kmeans": LabelKmeansArgs,
@@ -307,8 +308,8 @@ class MeshCcArgs(C.Structure):
                 ("inv_unit", F64)]
 
 
-MESH_CC_ABI_VERSION = 1    # include/mli_mesh_cc.h MLI_MESH_CC_ABI_VERSION
-MESH_CC_MAX_ROUNDS = 4096  # MLI_CC_MAX_ROUNDS
+MESH_CC_ABI_VERSION = 1
+MESH_CC_MAX_ROUNDS = 4096
 
 # the connected-component ops, versioned apart from the three ABIs above
 MESH_CC_ENTRY_POINTS = {"mli_cc_init": MeshCcArgs, "mli_cc_round": MeshCcArgs, "mli_cc_stats": MeshCcArgs}
@@ -322,12 +323,12 @@ class MetricsArgs(C.Structure):
                 ("ssim_channels", P), ("prep_pred", P), ("prep_target", P), ("partial", P)]
 
 
-METRICS_ABI_VERSION = 1      # include/mli_metrics.h MLI_METRICS_ABI_VERSION
-METRICS_MAX_SIDE = 16384     # MLI_METRICS_MAX_SIDE
-METRICS_MAX_IMAGES = 16383   # MLI_METRICS_MAX_IMAGES
-METRICS_MAX_CHANNELS = 4     # MLI_METRICS_MAX_CHANNELS
-METRICS_WINDOW = 7           # MLI_METRICS_WINDOW
-METRICS_TILE = (32, 8)       # MLI_METRICS_TILE_X, MLI_METRICS_TILE_Y
+METRICS_ABI_VERSION = 1
+METRICS_MAX_SIDE = 16384
+METRICS_MAX_IMAGES = 16383
+METRICS_MAX_CHANNELS = 4
+METRICS_WINDOW = 7
+METRICS_TILE = (32, 8)
 
 # the image-metric op, versioned apart from the four ABIs above
 METRICS_ENTRY_POINTS = {"mli_image_metrics": MetricsArgs}
@@ -351,7 +352,7 @@ class LightShadowsArgs(C.Structure):
                 ("normal_x_light", P), ("pseudo_shading", P)]
 
 
-RELIGHT_ABI_VERSION = 1      # include/mli_relight.h MLI_RELIGHT_ABI_VERSION
+RELIGHT_ABI_VERSION = 1
 
 # the multi-light ops, versioned apart from the five ABIs above; none needs scratch
 RELIGHT_ENTRY_POINTS = {"mli_light_points": LightPointsArgs, "mli_camera_hit": CameraHitArgs,
@@ -369,18 +370,64 @@ class LpipsArgs(C.Structure):
                 ("scratch", P)]
 
 
-LPIPS_ABI_VERSION = 1        # include/mli_lpips.h MLI_LPIPS_ABI_VERSION
-LPIPS_MIN_SIDE = 31          # MLI_LPIPS_MIN_SIDE
-LPIPS_MAX_SIDE = 4096        # MLI_LPIPS_MAX_SIDE
-LPIPS_MAX_PAIRS = 64         # MLI_LPIPS_MAX_PAIRS
-LPIPS_LAYERS = 5             # MLI_LPIPS_LAYERS
-LPIPS_TILE = (64, 64, 16)    # MLI_LPIPS_TILE_M, MLI_LPIPS_TILE_N, MLI_LPIPS_TILE_K
-LPIPS_K1_PADDED = 368        # MLI_LPIPS_K1_PADDED
-LPIPS_DIST_PIXELS = 16       # MLI_LPIPS_DIST_PIXELS
+LPIPS_ABI_VERSION = 1
+LPIPS_MIN_SIDE = 31
+LPIPS_MAX_SIDE = 4096
+LPIPS_MAX_PAIRS = 64
+LPIPS_LAYERS = 5
+LPIPS_TILE = (64, 64, 16)
+LPIPS_K1_PADDED = 368
+LPIPS_DIST_PIXELS = 16
 
 # the LPIPS op, versioned apart from the ABIs above
 LPIPS_ENTRY_POINTS = {"mli_lpips_pack": LpipsPackArgs, "mli_lpips": LpipsArgs}
 LPIPS_WORKSPACE = {"mli_lpips_pack": 1, "mli_lpips": 1}
+
+# One row per header of include/: what lib() binds and checks, and what tests/test_abi.py compares
+# with the header itself.  macros: header macro -> the constant above that mirrors it.
+ABI = namedtuple("ABI", "header version_macro version version_fn entry_points workspace macros")
+ABIS = (
+    ABI("mli_hip.h", "MLI_ABI_VERSION", ABI_VERSION, "mli_abi_version", ENTRY_POINTS, WORKSPACE,
+        {"MLI_Q4_SCALE": Q4_SCALE, "MLI_WGRAD_LAYOUT_ROWS": ROWS, "MLI_WGRAD_LAYOUT_TILED": TILED,
+         "MLI_WGRAD_LAYOUT_FRAG_ACC": FRAG_ACC, "MLI_WGRAD_LAYOUT_FRAG_NAT": FRAG_NAT}),
+    ABI("mli_mesh.h", "MLI_MESH_ABI_VERSION", MESH_ABI_VERSION, "mli_mesh_abi_version", MESH_ENTRY_POINTS,
+        MESH_WORKSPACE, {"MLI_MC_CHUNK": MC_CHUNK}),
+    ABI("mli_labels.h", "MLI_LABELS_ABI_VERSION", LABELS_ABI_VERSION, "mli_labels_abi_version", LABELS_ENTRY_POINTS,
+        LABELS_WORKSPACE,
+        {"MLI_LABELS_MAX_RADIUS": LABELS_MAX_RADIUS, "MLI_LABELS_MAX_K": LABELS_MAX_K,
+         "MLI_LABELS_TILE_X": LABELS_TILE[0], "MLI_LABELS_TILE_Y": LABELS_TILE[1],
+         "MLI_LABELS_DONOR_TILE": LABELS_DONOR_TILE, "MLI_LABELS_MAX_SLICES": LABELS_MAX_SLICES}),
+    ABI("mli_mesh_cc.h", "MLI_MESH_CC_ABI_VERSION", MESH_CC_ABI_VERSION, "mli_mesh_cc_abi_version",
+        MESH_CC_ENTRY_POINTS, MESH_CC_WORKSPACE, {"MLI_CC_MAX_ROUNDS": MESH_CC_MAX_ROUNDS}),
+    ABI("mli_metrics.h", "MLI_METRICS_ABI_VERSION", METRICS_ABI_VERSION, "mli_metrics_abi_version",
+        METRICS_ENTRY_POINTS, METRICS_WORKSPACE,
+        {"MLI_METRICS_MAX_SIDE": METRICS_MAX_SIDE, "MLI_METRICS_MAX_IMAGES": METRICS_MAX_IMAGES,
+         "MLI_METRICS_MAX_CHANNELS": METRICS_MAX_CHANNELS, "MLI_METRICS_WINDOW": METRICS_WINDOW,
+         "MLI_METRICS_TILE_X": METRICS_TILE[0], "MLI_METRICS_TILE_Y": METRICS_TILE[1]}),
+    ABI("mli_relight.h", "MLI_RELIGHT_ABI_VERSION", RELIGHT_ABI_VERSION, "mli_relight_abi_version",
+        RELIGHT_ENTRY_POINTS, RELIGHT_WORKSPACE, {}),
+    ABI("mli_lpips.h", "MLI_LPIPS_ABI_VERSION", LPIPS_ABI_VERSION, "mli_lpips_abi_version", LPIPS_ENTRY_POINTS,
+        LPIPS_WORKSPACE,
+        {"MLI_LPIPS_MIN_SIDE": LPIPS_MIN_SIDE, "MLI_LPIPS_MAX_SIDE": LPIPS_MAX_SIDE,
+         "MLI_LPIPS_MAX_PAIRS": LPIPS_MAX_PAIRS, "MLI_LPIPS_LAYERS": LPIPS_LAYERS, "MLI_LPIPS_TILE_M": LPIPS_TILE[0],
+         "MLI_LPIPS_TILE_N": LPIPS_TILE[1], "MLI_LPIPS_TILE_K": LPIPS_TILE[2], "MLI_LPIPS_K1_PADDED": LPIPS_K1_PADDED,
+         "MLI_LPIPS_DIST_PIXELS": LPIPS_DIST_PIXELS}),
+)
+
+
+def _merged(table):
+    """The rows' entry-point or workspace dicts as one; a name belongs to one ABI."""
+    out = {}
+    for abi in ABIS:
+        for name, value in getattr(abi, table).items():
+            if name in out:
+                raise ImportError("%s is in the %s table of two ABIs (the second: %s)" % (name, table, abi.header))
+            out[name] = value
+    return out
+
+
+_merged("entry_points")   # for its check alone: lib() binds row by row
+_WORKSPACE_COUNTS = _merged("workspace")
 
 _lib = None
 
@@ -392,37 +439,23 @@ def lib():
             raise ImportError("libmli_hip.so is not built (%s); run mli_nerf_amd.build.build() -- "
                               "there is no CPU fallback for the hot path" % LIB_PATH)
         _lib = C.CDLL(LIB_PATH)
-        for name, st in list(ENTRY_POINTS.items()) + list(MESH_ENTRY_POINTS.items()) + list(
-                LABELS_ENTRY_POINTS.items()) + list(MESH_CC_ENTRY_POINTS.items()) + list(
-                METRICS_ENTRY_POINTS.items()) + list(RELIGHT_ENTRY_POINTS.items()) + list(
-                LPIPS_ENTRY_POINTS.items()):
-            fn = getattr(_lib, name)
-            fn.argtypes = [C.POINTER(st), P]
-            fn.restype = I32
-        for table, points in ((WORKSPACE, ENTRY_POINTS), (MESH_WORKSPACE, MESH_ENTRY_POINTS),
-                              (LABELS_WORKSPACE, LABELS_ENTRY_POINTS), (MESH_CC_WORKSPACE, MESH_CC_ENTRY_POINTS),
-                              (METRICS_WORKSPACE, METRICS_ENTRY_POINTS), (LPIPS_WORKSPACE, LPIPS_ENTRY_POINTS)):
-            for name in table:
-                fn = getattr(_lib, name + "_workspace")
-                fn.argtypes = [C.POINTER(points[name]), C.POINTER(I64)]
-                fn.restype = I32
-        _lib.mli_mesh_abi_version.restype = I32
-        _lib.mli_labels_abi_version.restype = I32
-        _lib.mli_mesh_cc_abi_version.restype = I32
-        _lib.mli_metrics_abi_version.restype = I32
-        _lib.mli_relight_abi_version.restype = I32
-        _lib.mli_lpips_abi_version.restype = I32
-        _lib.mli_abi_version.restype = I32
         _lib.mli_error_string.restype = C.c_char_p
         _lib.mli_error_string.argtypes = [I32]
         _lib.mli_source_hash.restype = C.c_char_p
-        if (_lib.mli_abi_version() != ABI_VERSION or _lib.mli_mesh_abi_version() != MESH_ABI_VERSION
-                or _lib.mli_labels_abi_version() != LABELS_ABI_VERSION
-                or _lib.mli_mesh_cc_abi_version() != MESH_CC_ABI_VERSION
-                or _lib.mli_metrics_abi_version() != METRICS_ABI_VERSION
-                or _lib.mli_relight_abi_version() != RELIGHT_ABI_VERSION
-                or _lib.mli_lpips_abi_version() != LPIPS_ABI_VERSION):
-            raise ImportError("libmli_hip.so ABI mismatch")
+        for abi in ABIS:
+            for name, st in abi.entry_points.items():
+                fn = getattr(_lib, name)
+                fn.argtypes = [C.POINTER(st), P]
+                fn.restype = I32
+            for name in abi.workspace:
+                fn = getattr(_lib, name + "_workspace")
+                fn.argtypes = [C.POINTER(abi.entry_points[name]), C.POINTER(I64)]
+                fn.restype = I32
+            version = getattr(_lib, abi.version_fn)
+            version.restype = I32
+            if version() != abi.version:
+                raise ImportError("libmli_hip.so ABI mismatch: %s of include/%s is %d in _lib.py, the library was "
+                                  "built with %d" % (abi.version_macro, abi.header, abi.version, version()))
         from . import build as _build
         # in-tree sources: the in-tree library must match them.  Only a library OUTSIDE the in-tree
         # build output (an experiment build named by MLI_HIP_LIB, built from a modified tree on
@@ -454,9 +487,7 @@ def workspace(name, args):
     rc = getattr(lib(), name + "_workspace")(C.byref(args), out)
     if rc != 0:
         raise RuntimeError("%s_workspace failed: %s (%d)" % (name, lib().mli_error_string(rc).decode(), rc))
-    return [int(out[i]) for i in range(WORKSPACE.get(name) or MESH_WORKSPACE.get(name) or LABELS_WORKSPACE.get(name)
-                                         or MESH_CC_WORKSPACE.get(name) or METRICS_WORKSPACE.get(name)
-                                         or LPIPS_WORKSPACE[name])]
+    return [int(out[i]) for i in range(_WORKSPACE_COUNTS[name])]
 
 
 def ptr(t):

@@ -163,9 +163,6 @@ SWITCHES = (
     # which their zero weights make irrelevant.  No effect with elide_outside
     # off.  MLI_ELIDE_OUTSIDE_SAMPLING=0: the dense sampler
     ("elide_outside_sampling", "MLI_ELIDE_OUTSIDE_SAMPLING", True, bool),
-)
-# ... continued (rows of the same form, read and overridden the same way):
-MORE_SWITCHES = (
     # with skip_zero_tiles: the heads and their backward take the nonzero tiles too, eight to a
     # workgroup (mli_rgb_fwd_args.wtile_list; q4 then holds one item per nonzero tile and mli_dw4
     # forms the per-ray sums), equal up to the sign of a zero.  No effect with
@@ -234,7 +231,7 @@ class RenderEngine(_Lanes):
         # fixed-order reductions instead of fp32 atomics in mli_wgrad / mli_hash_bwd:
         # bit-reproducible gradients at the cost of partial-slab traffic
         self.deterministic = False
-        for name, env, default, kind in SWITCHES + MORE_SWITCHES:
+        for name, env, default, kind in SWITCHES:
             v = os.environ.get(env)
             setattr(self, name, default if v is None else int(v) if kind is int else v != "0")
         # stage-b training: the output layers' dW from per-tile partials the heads forward forms

@@ -28,7 +28,7 @@ import torch
 import torch.nn.functional as F
 
 from . import layout
-from .engine import MORE_SWITCHES, SWITCHES, PathConfig, RenderEngine
+from .engine import SWITCHES, PathConfig, RenderEngine
 from .hashgrid import GRID_DEFAULTS, level_table
 
 
@@ -254,7 +254,7 @@ class Model(torch.nn.Module):
         self.image_width = self.image_size_train[1]
         self.deterministic = False  # fixed-order gradient reductions (RenderEngine.deterministic)
         self.pq = True              # stage-b output-layer dW from the forward's partials (RenderEngine.pq)
-        for name, _, _, _ in SWITCHES + MORE_SWITCHES:   # a value other than None overrides the engine's (prepare)
+        for name, _, _, _ in SWITCHES:   # a value other than None overrides the engine's (prepare)
             setattr(self, name, None)
 
     # -------------------------------------------------------------- parameter plumbing
@@ -381,7 +381,7 @@ class Model(torch.nn.Module):
         eng = self.engine
         eng.deterministic = self.deterministic
         eng.pq = self.pq
-        for name, _, _, _ in SWITCHES + MORE_SWITCHES:
+        for name, _, _, _ in SWITCHES:
             if getattr(self, name) is not None:
                 setattr(eng, name, getattr(self, name))
         eng.set_normal_eps(sdf.normal_eps)

@@ -1,79 +1,116 @@
-"""C-ABI boundary checks that need no GPU: the ctypes mirrors in mli_nerf_amd/_lib.py have
-the same size and field offsets as the structs gcc lays out from include/mli_hip.h, and the
-built libmli_hip.so loads and exports every entry point the header declares (no compute
-calls are made)."""
+"""C-ABI boundary checks that need no GPU, over every row of mli_nerf_amd/_lib.py's ABIS (one per
+header of include/): the ctypes mirrors have the sizes and field offsets gcc lays out, the
+constants equal the header's macros, every declared struct is mirrored, the declared functions are
+the row's entry points, workspace queries and version function, and the built libmli_hip.so
+exports them (no compute calls are made).  The ABI versions are pinned here, in PINNED, and nowhere
+else in tests/."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
+import abi_check as A
 from mli_nerf_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mli_hip.h")
 
-STRUCTS = {
-    "mli_grid_levels": L.GridLevels, "mli_rays_args": L.RaysArgs, "mli_hashgrid_args": L.HashgridArgs,
-    "mli_sdf_args": L.SdfArgs, "mli_sample_coarse_args": L.SampleCoarseArgs,
-    "mli_sample_fine_args": L.SampleFineArgs, "mli_rgb_fwd_args": L.RgbFwdArgs,
-    "mli_composite_args": L.CompositeArgs, "mli_composite_bwd_args": L.CompositeBwdArgs,
-    "mli_rgb_bwd_args": L.RgbBwdArgs, "mli_wgrad_job": L.WgradJob, "mli_wgrad_args": L.WgradArgs,
-    "mli_pack_layer": L.PackLayer, "mli_pack_args": L.PackArgs, "mli_pack_sdf_args": L.PackSdfArgs,
-    "mli_assemble_layer": L.AssembleLayer, "mli_assemble_args": L.AssembleArgs,
-    "mli_adamw_args": L.AdamwArgs, "mli_cast_args": L.CastArgs, "mli_loss_args": L.LossArgs,
-    "mli_composite_bwd_geo_args": L.CompositeBwdGeoArgs, "mli_geo_bwd_args": L.GeoBwdArgs,
-    "mli_sdf_bwd_args": L.SdfBwdArgs, "mli_pack_sdf_t_args": L.PackSdfTArgs, "mli_hash_bwd_args": L.HashBwdArgs,
-    "mli_frag_rows_args": L.FragRowsArgs, "mli_light_visibility_args": L.LightVisibilityArgs,
-    "mli_ray_batch_args": L.RayBatchArgs, "mli_dw4_args": L.Dw4Args,
-    "mli_composite_loss_args": L.CompositeLossArgs,
-}
+# a change of a header's layouts or semantics moves its number here, in the header and in _lib.py
+PINNED = {"mli_hip.h": 18, "mli_mesh.h": 1, "mli_labels.h": 1, "mli_mesh_cc.h": 1, "mli_metrics.h": 1,
+          "mli_relight.h": 1, "mli_lpips.h": 1}
+
+# mirrored structs that are no entry point's argument (nested in one, or an array it points to)
+STRUCTS = {"mli_hip.h": {"mli_grid_levels": L.GridLevels, "mli_wgrad_job": L.WgradJob,
+                         "mli_pack_layer": L.PackLayer, "mli_assemble_layer": L.AssembleLayer}}
+# declared functions beside a row's entry points, workspace queries and version function
+MORE_FUNCTIONS = {"mli_hip.h": {"mli_error_string", "mli_source_hash"}}
+
+needs_lib = pytest.mark.skipif(not os.path.exists(L.LIB_PATH), reason="libmli_hip.so not built")
+every_abi = pytest.mark.parametrize("abi", L.ABIS, ids=[abi.header for abi in L.ABIS])
 
 
-def _declared_functions():
-    src = open(HEADER).read()
-    return sorted(set(re.findall(r"^(?:int|const char\*)\s+(mli_\w+)\s*\(", src, re.M)))
+def mirrored(abi):
+    """{C name: ctypes mirror} of a row: the struct the header gives each entry point (and its
+    workspace query), and the row's STRUCTS."""
+    args = A.arg_structs(abi.header)
+    out = dict(STRUCTS.get(abi.header, {}))
+    for fn, st in abi.entry_points.items():
+        assert out.setdefault(args[fn], st) is st, fn
+    for fn in abi.workspace:
+        assert args[fn + "_workspace"] == args[fn], fn
+    return out
 
 
-def test_struct_layout_matches_gcc(tmp_path):
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mli_hip.h"', "int main(void) {"]
-    for cname, st in STRUCTS.items():
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+def functions(abi):
+    return (set(abi.entry_points) | {n + "_workspace" for n in abi.workspace} | {abi.version_fn}
+            | MORE_FUNCTIONS.get(abi.header, set()))
+
+
+@pytest.fixture(scope="module")
+def gcc(tmp_path_factory):
+    """One compilation for all rows: every header, every mirrored struct, every mirrored macro."""
+    structs, macros = {}, []
+    for abi in L.ABIS:
+        structs.update(mirrored(abi))
+        macros += [abi.version_macro] + list(abi.macros)
+    assert len(macros) == len(set(macros))
+    return A.gcc_layout([abi.header for abi in L.ABIS], structs, macros, tmp_path_factory.mktemp("abi"))
+
+
+@every_abi
+def test_struct_layout_matches_gcc(abi, gcc):
+    for cname, st in mirrored(abi).items():
+        assert gcc[cname] == C.sizeof(st), cname
         for f in st._fields_:
-            lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, f[0], cname, f[0]))
-    lines += ["return 0; }"]
-    c = tmp_path / "abi.c"
-    c.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.dirname(HEADER), str(c), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True,
-                                                  text=True).stdout.splitlines())
-    for cname, st in STRUCTS.items():
-        assert int(got[cname]) == C.sizeof(st), cname
-        for f in st._fields_:
-            assert int(got["%s.%s" % (cname, f[0])]) == getattr(st, f[0]).offset, (cname, f[0])
+            assert gcc["%s.%s" % (cname, f[0])] == getattr(st, f[0]).offset, (cname, f[0])
+    for m, v in abi.macros.items():
+        assert gcc[m] == v, m
 
 
-def test_every_header_struct_is_mirrored():
-    src = open(HEADER).read()
-    declared = set(re.findall(r"}\s*(mli_\w+)\s*;", src))
-    assert declared == set(STRUCTS), declared ^ set(STRUCTS)
+@every_abi
+def test_every_header_struct_is_mirrored(abi):
+    declared = A.declared_structs(abi.header)
+    assert declared == set(mirrored(abi)), declared ^ set(mirrored(abi))
 
 
-def test_library_exports_header_entry_points():
-    if not os.path.exists(L.LIB_PATH):
-        pytest.skip("libmli_hip.so not built (run __graft_entry__.build())")
-    lib = L.lib()  # loads, binds argtypes and checks the ABI version
-    assert lib.mli_abi_version() == L.ABI_VERSION
-    fns = _declared_functions()
-    queries = {n + "_workspace" for n in L.WORKSPACE}
-    assert set(L.ENTRY_POINTS) | {"mli_abi_version", "mli_error_string", "mli_source_hash"} | queries == set(fns)
-    for name in fns:
+@every_abi
+def test_declared_functions_are_the_rows(abi):
+    assert A.declared_functions(abi.header) == functions(abi)
+    assert set(abi.workspace) <= set(abi.entry_points)
+
+
+def test_no_function_is_declared_twice():
+    names = [fn for abi in L.ABIS for fn in sorted(A.declared_functions(abi.header))]
+    assert len(names) == len(set(names)) > 60
+    assert len(set(PINNED)) == len(L.ABIS) == len({abi.header for abi in L.ABIS})
+
+
+@every_abi
+def test_version_is_pinned(abi, gcc):
+    assert gcc[abi.version_macro] == abi.version == PINNED[abi.header]
+
+
+@needs_lib
+@every_abi
+def test_library_exports_header_entry_points(abi):
+    lib = L.lib()  # loads, binds argtypes and checks the ABI versions
+    assert getattr(lib, abi.version_fn)() == abi.version == PINNED[abi.header]
+    for name in A.declared_functions(abi.header):
         assert hasattr(lib, name), name
+
+
+@needs_lib
+def test_library_names_its_errors_and_its_sources():
+    lib = L.lib()
     assert lib.mli_error_string(0)
     from mli_nerf_amd import build as B
     assert lib.mli_source_hash().decode() == B.source_hash() == B.built_hash(L.LIB_PATH)
+
+
+def test_appended_optional_fields_are_the_last_ones():
+    assert [f[0] for f in L.SdfArgs._fields_[-2:]] == ["inside_list", "n_inside"]
+    for st in (L.RgbFwdArgs, L.RgbBwdArgs, L.Dw4Args, L.LiveTilesArgs):
+        assert st._fields_[-1][0] in ("n_wtiles_pad", "wtile_rank"), st
 
 
 def test_product_path_does_not_import_oracle():

@@ -82,7 +82,8 @@ def test_switch_table():
                     "MLI_LIVE_TILES_PASS": ("live_tiles_pass", 1, int),
                     "MLI_SKIP_ZERO_TILES": ("skip_zero_tiles", True, bool),
                     "MLI_ELIDE_OUTSIDE": ("elide_outside", True, bool),
-                    "MLI_ELIDE_OUTSIDE_SAMPLING": ("elide_outside_sampling", True, bool)}
+                    "MLI_ELIDE_OUTSIDE_SAMPLING": ("elide_outside_sampling", True, bool),
+                    "MLI_SKIP_ZERO_TILES_HEADS": ("skip_zero_tiles_heads", True, bool)}
     cfg = preset("syn_hotdog_b", rays=64, n_coarse=16, n_fine=4, log2T=14)
     model = Model(cfg.model, cfg.data)
     for attr, env, default, kind in E.SWITCHES:

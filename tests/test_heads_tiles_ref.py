@@ -1,20 +1,12 @@
 """The padded nonzero-tile list (tests/heads_tiles_ref.py, the restatement mli_live_tiles'
 n_wtiles_pad output is tested against in test_gpu_heads_tiles.py) against a scalar loop over random
-flag words, and the layouts of the structs that carry the lists (CPU)."""
-import ctypes as C
-import os
-import subprocess
-
+flag words (CPU)."""
 import numpy as np
 import pytest
-
-from mli_nerf_amd import _lib as L
 
 from heads_tiles_ref import padded_tiles
 from live_tiles_ref import live_tiles
 from test_live_tiles_ref import weights_from_tiles
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _scalar_scan(flags, T):
@@ -92,23 +84,3 @@ def test_edges(N):
     W, n = _check(flags, N)
     assert W == 7 and n == 8
 
-
-@pytest.mark.parametrize("cname,st", (("mli_rgb_fwd_args", L.RgbFwdArgs), ("mli_rgb_bwd_args", L.RgbBwdArgs),
-                                      ("mli_dw4_args", L.Dw4Args), ("mli_live_tiles_args", L.LiveTilesArgs)))
-def test_struct_layouts_match_gcc(tmp_path, cname, st):
-    """The structs with appended fields against their ctypes mirrors, by compiling."""
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mli_hip.h"', "int main(void) {",
-             'printf("%s %%zu\\n", sizeof(%s));' % (cname, cname)]
-    for f in st._fields_:
-        lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, f[0], cname, f[0]))
-    lines += ["return 0; }"]
-    c = tmp_path / "abi.c"
-    c.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True,
-                                                  text=True).stdout.splitlines())
-    assert int(got[cname]) == C.sizeof(st)
-    for f in st._fields_:
-        assert int(got["%s.%s" % (cname, f[0])]) == getattr(st, f[0]).offset, f[0]
-    assert st._fields_[-1][0] in ("n_wtiles_pad", "wtile_rank")

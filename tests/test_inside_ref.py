@@ -1,22 +1,15 @@
 """The inside-ray list (tests/inside_ref.py, the restatement mli_inside_list and the FIELD pass of
-mli_sdf are tested against in test_gpu_field_inside.py) against a brute-force loop, the layout of
-its args struct, and the premise of the elision: the share of the benchmark's rays that miss the
+mli_sdf are tested against in test_gpu_field_inside.py) against a brute-force loop, and the
+premise of the elision: the share of the benchmark's rays that miss the
 bounding sphere (CPU)."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
-from mli_nerf_amd import _lib as L
 from mli_nerf_amd import synthetic
 from oracle import render as o_render
 
 from inside_ref import inside_list, patterns, tile_map
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def brute(outside, N, n_pad=0):
@@ -74,25 +67,3 @@ def test_outside_share_of_the_benchmark_batches(frame):
     lst, n = inside_list(outside.reshape(-1).numpy())
     assert n == 4096 - int(outside.sum())
 
-
-def test_args_struct_layout_matches_gcc(tmp_path):
-    """mli_inside_list_args and the list fields of mli_sdf_args against their ctypes mirrors, by
-    compiling (as tests/test_abi.py does for the structs it lists)."""
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mli_hip.h"', "int main(void) {"]
-    structs = {"mli_inside_list_args": L.InsideListArgs, "mli_sdf_args": L.SdfArgs}
-    for cname, st in structs.items():
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
-        for f in st._fields_:
-            lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, f[0], cname, f[0]))
-    lines += ["return 0; }"]
-    c = tmp_path / "abi.c"
-    c.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True,
-                                                  text=True).stdout.splitlines())
-    for cname, st in structs.items():
-        assert int(got[cname]) == C.sizeof(st), cname
-        for f in st._fields_:
-            assert int(got["%s.%s" % (cname, f[0])]) == getattr(st, f[0]).offset, (cname, f[0])
-    assert [f[0] for f in L.SdfArgs._fields_[-2:]] == ["inside_list", "n_inside"]

@@ -1,11 +1,10 @@
-"""C-ABI boundary of the pseudo-label ops (include/mli_labels.h), no GPU: the ctypes mirror has
-gcc's layout, the library exports what the header declares, the workspace queries give what
-pseudo_label.py allocates, bad shapes are refused by the host check (which launches nothing), and
-the label file makes its round trip into the dataset's pseudo elements."""
+"""C-ABI boundary of the pseudo-label ops (include/mli_labels.h), no GPU: the workspace queries
+give what pseudo_label.py allocates, bad shapes are refused by the host check (which launches
+nothing), and the label file makes its round trip into the dataset's pseudo elements.  The layout,
+export and version checks every header gets are in tests/test_abi.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 import torch
@@ -13,67 +12,7 @@ import torch
 from mli_nerf_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mli_labels.h")
-STRUCTS = {"mli_label_morph_args": L.LabelMorphArgs, "mli_label_kmeans_args": L.LabelKmeansArgs,
-           "mli_label_best_ref_args": L.LabelBestRefArgs, "mli_label_fill_args": L.LabelFillArgs}
-MACROS = {"MLI_LABELS_ABI_VERSION": L.LABELS_ABI_VERSION, "MLI_LABELS_MAX_RADIUS": L.LABELS_MAX_RADIUS,
-          "MLI_LABELS_MAX_K": L.LABELS_MAX_K, "MLI_LABELS_TILE_X": L.LABELS_TILE[0],
-          "MLI_LABELS_TILE_Y": L.LABELS_TILE[1], "MLI_LABELS_DONOR_TILE": L.LABELS_DONOR_TILE,
-          "MLI_LABELS_MAX_SLICES": L.LABELS_MAX_SLICES}
-
 needs_lib = pytest.mark.skipif(not os.path.exists(L.LIB_PATH), reason="libmli_hip.so not built")
-
-
-def _declared_functions():
-    return sorted(set(re.findall(r"^(?:int|const char\*)\s+(mli_\w+)\s*\(", open(HEADER).read(), re.M)))
-
-
-def test_struct_layout_matches_gcc(tmp_path):
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mli_labels.h"', '#include "mli_mesh.h"',
-             "int main(void) {"]
-    for cname, st in STRUCTS.items():
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
-        for f in st._fields_:
-            lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, f[0], cname, f[0]))
-    for m in list(MACROS) + ["MLI_ABI_VERSION", "MLI_MESH_ABI_VERSION"]:
-        lines.append('printf("%s %%d\\n", %s);' % (m, m))
-    lines += ["return 0; }"]
-    c = tmp_path / "abi.c"
-    c.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.dirname(HEADER), str(c), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True,
-                                                  text=True).stdout.splitlines())
-    for cname, st in STRUCTS.items():
-        assert int(got[cname]) == C.sizeof(st), cname
-        for f in st._fields_:
-            assert int(got["%s.%s" % (cname, f[0])]) == getattr(st, f[0]).offset, (cname, f[0])
-    for m, v in MACROS.items():
-        assert int(got[m]) == v, m
-    # the three ABI versions: the new one starts at 1, the other two did not move
-    assert int(got["MLI_LABELS_ABI_VERSION"]) == L.LABELS_ABI_VERSION == 1
-    assert int(got["MLI_ABI_VERSION"]) == L.ABI_VERSION == 18
-    assert int(got["MLI_MESH_ABI_VERSION"]) == L.MESH_ABI_VERSION == 1
-
-
-def test_every_header_struct_is_mirrored():
-    declared = set(re.findall(r"}\s*(mli_\w+)\s*;", open(HEADER).read()))
-    assert declared == set(STRUCTS)
-    assert {st for st in L.LABELS_ENTRY_POINTS.values()} == set(STRUCTS.values())
-    others = set(L.ENTRY_POINTS) | set(L.MESH_ENTRY_POINTS)
-    assert not set(L.LABELS_ENTRY_POINTS) & others
-    assert not set(L.LABELS_WORKSPACE) & (set(L.WORKSPACE) | set(L.MESH_WORKSPACE))
-
-
-@needs_lib
-def test_library_exports_header_entry_points():
-    lib = L.lib()
-    assert lib.mli_labels_abi_version() == L.LABELS_ABI_VERSION
-    assert lib.mli_abi_version() == 18 and lib.mli_mesh_abi_version() == 1
-    queries = {n + "_workspace" for n in L.LABELS_WORKSPACE}
-    assert set(L.LABELS_ENTRY_POINTS) | queries | {"mli_labels_abi_version"} == set(_declared_functions())
-    for name in _declared_functions():
-        assert hasattr(lib, name), name
 
 
 @needs_lib

@@ -1,17 +1,9 @@
 """Properties of the live-ray compaction (tests/live_ref.py, the restatement mli_live_rays is
-tested against bit for bit in test_gpu_live_rays.py), and the layout of its args struct (CPU)."""
-import ctypes as C
-import os
-import subprocess
-
+tested against bit for bit in test_gpu_live_rays.py) (CPU)."""
 import numpy as np
 import pytest
 
-from mli_nerf_amd import _lib as L
-
 from live_ref import live_flags, live_rays
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def patterns(R):
@@ -84,22 +76,3 @@ def test_rejects_other_shapes():
         with pytest.raises(ValueError):
             live_rays(np.zeros((N, R), np.float32))
 
-
-def test_args_struct_layout_matches_gcc(tmp_path):
-    """mli_live_rays_args against its ctypes mirror, by compiling (as tests/test_abi.py does for
-    the structs it lists)."""
-    st, cname = L.LiveRaysArgs, "mli_live_rays_args"
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mli_hip.h"', "int main(void) {",
-             'printf("%s %%zu\\n", sizeof(%s));' % (cname, cname)]
-    for f in st._fields_:
-        lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, f[0], cname, f[0]))
-    lines += ["return 0; }"]
-    c = tmp_path / "abi.c"
-    c.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True,
-                                                  text=True).stdout.splitlines())
-    assert int(got[cname]) == C.sizeof(st)
-    for f in st._fields_:
-        assert int(got["%s.%s" % (cname, f[0])]) == getattr(st, f[0]).offset, f[0]

@@ -1,18 +1,11 @@
 """The nonzero-tile lists (tests/live_tiles_ref.py, the restatement mli_live_tiles is tested
-against in test_gpu_live_tiles.py) on hand-made weights, and the layout of the args struct (CPU)."""
-import ctypes as C
-import os
-import subprocess
-
+against in test_gpu_live_tiles.py) on hand-made weights (CPU)."""
 import numpy as np
 import pytest
-
-from mli_nerf_amd import _lib as L
 
 from live_ref import live_rays
 from live_tiles_ref import live_tiles, tile_flags
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NS = (32, 128, 256)
 
 
@@ -119,22 +112,3 @@ def test_random(N):
     nz[rng.random(R) < 0.3] = False
     _check(weights_from_tiles(nz, N), nz)
 
-
-def test_args_struct_layout_matches_gcc(tmp_path):
-    """mli_live_tiles_args against its ctypes mirror, by compiling (as tests/test_abi.py does for
-    the structs it lists)."""
-    st, cname = L.LiveTilesArgs, "mli_live_tiles_args"
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mli_hip.h"', "int main(void) {",
-             'printf("%s %%zu\\n", sizeof(%s));' % (cname, cname)]
-    for f in st._fields_:
-        lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, f[0], cname, f[0]))
-    lines += ["return 0; }"]
-    c = tmp_path / "abi.c"
-    c.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True,
-                                                  text=True).stdout.splitlines())
-    assert int(got[cname]) == C.sizeof(st)
-    for f in st._fields_:
-        assert int(got["%s.%s" % (cname, f[0])]) == getattr(st, f[0]).offset, f[0]

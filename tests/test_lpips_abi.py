@@ -1,83 +1,20 @@
-"""C-ABI boundary of the LPIPS op (include/mli_lpips.h), no GPU: the ctypes mirrors have gcc's
-layout, the library exports what the header declares and shares no name with the other ABIs, the
-workspace queries give what lpips.py allocates, and bad shapes, bad pointer pairs, NULL buffers and
-partly set taps are refused by the host check (which launches nothing)."""
+"""C-ABI boundary of the LPIPS op (include/mli_lpips.h), no GPU: the workspace queries give what
+lpips.py allocates, and bad shapes, bad pointer pairs, NULL buffers and partly set taps are refused
+by the host check (which launches nothing).  The layout, export and version checks every header
+gets are in tests/test_abi.py."""
 import ctypes as C
 import os
-import re
-import subprocess
 
 import pytest
 
+from abi_check import declared_functions
 from mli_nerf_amd import _lib as L
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mli_lpips.h")
-STRUCTS = {"mli_lpips_pack_args": L.LpipsPackArgs, "mli_lpips_args": L.LpipsArgs}
-MACROS = {"MLI_LPIPS_ABI_VERSION": L.LPIPS_ABI_VERSION, "MLI_LPIPS_MIN_SIDE": L.LPIPS_MIN_SIDE,
-          "MLI_LPIPS_MAX_SIDE": L.LPIPS_MAX_SIDE, "MLI_LPIPS_MAX_PAIRS": L.LPIPS_MAX_PAIRS,
-          "MLI_LPIPS_LAYERS": L.LPIPS_LAYERS, "MLI_LPIPS_TILE_M": L.LPIPS_TILE[0], "MLI_LPIPS_TILE_N": L.LPIPS_TILE[1],
-          "MLI_LPIPS_TILE_K": L.LPIPS_TILE[2], "MLI_LPIPS_K1_PADDED": L.LPIPS_K1_PADDED,
-          "MLI_LPIPS_DIST_PIXELS": L.LPIPS_DIST_PIXELS}
-OTHER_HEADERS = ("mli_hip.h", "mli_mesh.h", "mli_mesh_cc.h", "mli_labels.h", "mli_metrics.h", "mli_relight.h")
 
 needs_lib = pytest.mark.skipif(not os.path.exists(L.LIB_PATH), reason="libmli_hip.so not built")
 
 
-def _functions(header):
-    return sorted(set(re.findall(r"^(?:int|const char\*)\s+(mli_\w+)\s*\(", open(header).read(), re.M)))
-
-
-def test_struct_layout_matches_gcc(tmp_path):
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mli_lpips.h"', '#include "mli_metrics.h"',
-             "int main(void) {"]
-    for cname, st in STRUCTS.items():
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
-        for f in st._fields_:
-            lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, f[0], cname, f[0]))
-    for m in list(MACROS) + ["MLI_ABI_VERSION", "MLI_METRICS_ABI_VERSION"]:
-        lines.append('printf("%s %%d\\n", %s);' % (m, m))
-    lines += ["return 0; }"]
-    c = tmp_path / "abi.c"
-    c.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.dirname(HEADER), str(c), "-o", str(exe)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True,
-                                                  text=True).stdout.splitlines())
-    for cname, st in STRUCTS.items():
-        assert int(got[cname]) == C.sizeof(st), cname
-        for f in st._fields_:
-            assert int(got["%s.%s" % (cname, f[0])]) == getattr(st, f[0]).offset, (cname, f[0])
-    for m, v in MACROS.items():
-        assert int(got[m]) == v, m
-    # the new ABI starts at 1; the ones it sits beside did not move
-    assert int(got["MLI_LPIPS_ABI_VERSION"]) == L.LPIPS_ABI_VERSION == 1
-    assert int(got["MLI_ABI_VERSION"]) == L.ABI_VERSION and int(got["MLI_METRICS_ABI_VERSION"]) == L.METRICS_ABI_VERSION
-
-
-def test_every_header_struct_is_mirrored_and_no_name_is_shared():
-    declared = set(re.findall(r"}\s*(mli_\w+)\s*;", open(HEADER).read()))
-    assert declared == set(STRUCTS)
-    assert set(L.LPIPS_ENTRY_POINTS.values()) == set(STRUCTS.values())
-    queries = {n + "_workspace" for n in L.LPIPS_WORKSPACE}
-    assert set(L.LPIPS_ENTRY_POINTS) | queries | {"mli_lpips_abi_version"} == set(_functions(HEADER))
-    others = set()
-    for h in OTHER_HEADERS:
-        others |= set(_functions(os.path.join(ROOT, "include", h)))
-    assert len(others) > 20 and not set(_functions(HEADER)) & others
-    tables = (set(L.ENTRY_POINTS) | set(L.MESH_ENTRY_POINTS) | set(L.LABELS_ENTRY_POINTS) | set(L.MESH_CC_ENTRY_POINTS)
-              | set(L.METRICS_ENTRY_POINTS) | set(L.RELIGHT_ENTRY_POINTS))
-    assert not set(L.LPIPS_ENTRY_POINTS) & tables
-    # the metrics header keeps its own function set
-    assert not any("lpips" in f for f in _functions(os.path.join(ROOT, "include", "mli_metrics.h")))
-
-
-@needs_lib
-def test_library_exports_header_entry_points():
-    lib = L.lib()
-    assert lib.mli_lpips_abi_version() == L.LPIPS_ABI_VERSION
-    for name in _functions(HEADER):
-        assert hasattr(lib, name), name
+def test_metrics_header_declares_no_lpips_function():
+    assert not any("lpips" in f for f in declared_functions("mli_metrics.h"))
 
 
 @needs_lib
